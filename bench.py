@@ -6,7 +6,12 @@ One "step" = one PPO iteration: 24 x (policy act on the fused MFMA MLP + lgx_ste
 5 epochs x 4 minibatches of PPO (fused f32-MFMA update, RCCL gradient all-reduce when N>1).
 value = 24 * envs_per_gpu * world * K / max-over-ranks wall time of K iterations.
 
-Launch: python bench.py [--gpus N --steps K --warmup W].  Under torch.distributed.run (one rank
+A plain run sets up, warms up, times the K iterations and prints the headline line; --full adds the
+event timing of the lgx kernels and PPO GEMMs over the timed region, the rooflines, the launches
+timed on their own after it and the CPU baseline.  --dump-outputs DIR writes the last timed
+iteration's results as DIR/<name>.npy (dump_outputs).
+
+Launch: python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR].  Under torch.distributed.run (one rank
 per GPU, env vars RANK/LOCAL_RANK/WORLD_SIZE/MASTER_*) WORLD_SIZE must equal --gpus; without a
 launcher, --gpus N > 1 starts the N ranks itself (torch.distributed.run as a child process, before
 anything touches the GPU), passes rank 0's JSON line through and exits with the launcher's code.
@@ -198,7 +203,16 @@ def parse():
     p.add_argument("--warmup", type=int, default=5)
     p.add_argument("--task", default="go1_rough")
     p.add_argument("--num_envs", type=int, default=4096)
-    p.add_argument("--no_cpu_baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="besides the headline figure: in-library kernel and PPO-GEMM event timing over the timed "
+                        "region, the rooflines, the isolated dW / standalone actuator-net launches, the all-reduce "
+                        "timing and the CPU baseline (a plain run only sets up, warms up, times the steps and prints "
+                        "the headline line)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last iteration left a caller of runner.learn() as "
+                        "DIR/<name>.npy (float32): the policy parameters, the env's observations and the last "
+                        "rollout's storage (a fixed seeded sample of envs), the last update's statistics")
+    p.add_argument("--no_cpu_baseline", action="store_true", help="with --full: skip the CPU baseline")
     p.add_argument("--cpu_envs", type=int, default=4096)
     p.add_argument("--actuator_net_torques", action="store_true",
                    help="ANYmal: the SEA actuator network as the torque source (cfg.control.explicit_torques)")
@@ -389,6 +403,7 @@ def data_parallel_check(runner, fused, comm_t, world, backend, device, dist):
         out["bucketed_allreduce"] = bool(fused.bucketed)
         out["join_events"] = fused.join_events   # cross-stream joins: "system" whenever data-parallel
         out["allreduce_impl"] = fused.allreduce_impl   # "lgx" = lgx_allreduce_grads (LGX_NATIVE_ALLREDUCE=1)
+    if fused is not None and comm_t is not None:   # (--full: the all-reduces were event-timed)
         n, ms, nbytes, mbs = comm_t
         mb_per_iter = alg.num_learning_epochs * alg.num_mini_batches
         out["allreduce"] = {"collectives_timed": n, "bytes_per_minibatch": (nbytes / mbs) if mbs else 0,
@@ -396,6 +411,46 @@ def data_parallel_check(runner, fused, comm_t, world, backend, device, dist):
                             "note": "HIP events around every gradient all-reduce of every k-th minibatch "
                                     "(LGX_BENCH_GEMM_TIMING), on the stream it is issued from"}
     return out
+
+
+DUMP_ENVS = 256            # --dump-outputs: envs of the storage sample
+DUMP_LIMIT = 64 << 20      # bytes, all files together
+
+
+def dump_outputs(path, runner, env, rank):
+    """--dump-outputs: what the last timed iteration left a caller of runner.learn(), as float32
+    <name>.npy files under `path` (ranks above 0 prefix theirs with rank<r>_): the flat policy
+    parameters after the last update, the env's current observations, and the last rollout's
+    storage ([T, envs, ...]; a fixed seeded sample of DUMP_ENVS envs, sorted) with the returns and
+    normalised advantages the update consumed; update_stats = (value loss, surrogate loss, learning
+    rate) of the last update, float64.  Seeds and arguments fix the inputs, so two builds can be
+    compared file by file."""
+    import numpy as np
+    import torch
+    alg, st = runner.alg, runner.alg.storage
+    rng = np.random.default_rng(0)
+    pick = np.sort(rng.choice(st.num_envs, min(DUMP_ENVS, st.num_envs), replace=False))
+    pick = torch.from_numpy(pick).to(st.observations.device)
+    arrays = {"policy_params": torch.cat([p.detach().reshape(-1) for p in alg.actor_critic.parameters()]),
+              "obs": env.get_observations()}
+    if env.get_privileged_observations() is not None:
+        arrays["privileged_obs"] = env.get_privileged_observations()
+    for name in ("observations", "privileged_observations", "actions", "rewards", "dones", "values", "returns",
+                 "advantages", "actions_log_prob", "mu", "sigma"):
+        t = getattr(st, name)
+        if t is not None:
+            arrays["storage_" + name] = t.index_select(1, pick)
+    arrays = {k: v.detach().to(torch.float32).cpu().numpy() for k, v in arrays.items()}
+    s = runner.last_iteration_stats
+    arrays["update_stats"] = np.array([s.get(k, float("nan")) for k in ("value_loss", "surrogate_loss", "learning_rate")],
+                                      dtype=np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT}-byte limit")
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, (f"rank{rank}_" if rank else "") + k + ".npy"), a)
+    return {"dir": path, "bytes": total, "arrays": {k: list(a.shape) for k, a in arrays.items()}}
 
 
 def _free_port():
@@ -507,9 +562,10 @@ def main():
     gc.collect()
     gc.disable()   # no collector pauses inside the timed region (host-side Python only)
     timing_period = int(os.environ.get("LGX_BENCH_KERNEL_TIMING", "7"))   # time every k-th env step (0: off); 7 is coprime with the 24-step rollout, so every step position (the cold first one included) is sampled in proportion
-    lib.lgx_profile_enable(handle, timing_period)
     fused = getattr(runner.alg, "_fused", None)
-    if fused is not None:   # HIP events around the PPO-update GEMM launches of every k-th minibatch
+    if args.full:
+        lib.lgx_profile_enable(handle, timing_period)
+    if args.full and fused is not None:   # HIP events around the PPO-update GEMM launches of every k-th minibatch
         fused.time_gemms(int(os.environ.get("LGX_BENCH_GEMM_TIMING", "7")))
     if distributed:
         dist.barrier()
@@ -521,14 +577,16 @@ def main():
         dist.barrier()
     elapsed = time.perf_counter() - t0
     gc.enable()
-    lib.lgx_profile_enable(handle, 0)
-    gemm_t = fused.gemm_timings() if fused is not None else {}
-    comm_t = fused.comm_timings() if fused is not None else None
-    if fused is not None:
-        fused.time_gemms(0)
+    dumped = dump_outputs(args.dump_outputs, runner, env, rank) if args.dump_outputs else None
+    gemm_t, comm_t = {}, None
     ms = (C.c_double * 3)()
     cnt = (C.c_int64 * 3)()
-    lgxlib.check(lib.lgx_profile_collect(handle, ms, cnt), "lgx_profile_collect")
+    if args.full:
+        lib.lgx_profile_enable(handle, 0)
+        lgxlib.check(lib.lgx_profile_collect(handle, ms, cnt), "lgx_profile_collect")
+    if args.full and fused is not None:
+        gemm_t, comm_t = fused.gemm_timings(), fused.comm_timings()
+        fused.time_gemms(0)
     if distributed:
         t = torch.tensor([elapsed], device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -538,6 +596,45 @@ def main():
     N = args.num_envs
     steps_per_iter = runner.num_steps_per_env
     value = steps_per_iter * N * world * args.steps / elapsed
+    it_ms = 1000.0 * elapsed / args.steps
+    out = {
+        "metric": (BASELINE_METRIC if (args.task == "go1_rough" and N == 4096)
+                   else f"env-steps/sec (whole node), {args.task} {N} envs/GPU"),
+        "value": value, "unit": "env-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": it_ms, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "fp32", "data": "synthetic (procedural curriculum terrain, random-init policy)",
+        "config": {"workload": WORKLOADS.get(args.task, args.task) +
+                               (", SEA actuator-net torques" if ctrl == "SEA" else "") +
+                               f", PPO {steps_per_iter} steps x {N} envs/GPU, "
+                               f"{runner.alg.num_learning_epochs} epochs x {runner.alg.num_mini_batches} minibatches",
+                   "envs_per_gpu": N, "global_envs": N * world, "parallelism": f"dp{world}"},
+        "full": args.full,
+    }
+    if args.full:
+        out.update(kernel_report(args, env, runner, lib, fused, gemm_t, ms, cnt, it_ms))
+    out["last_iteration"] = runner.last_iteration_stats
+    out["data_parallel"] = data_parallel
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
+        try:
+            out["cpu_baseline"] = cpu_baseline(args.task, args.cpu_envs)
+        except Exception as e:  # reported, never silently replaced
+            out["cpu_baseline"] = {"error": repr(e)}
+    if rank == 0:
+        print(json.dumps(out))
+    if distributed:
+        runner.close()
+        dist.destroy_process_group()
+
+
+def kernel_report(args, env, runner, lib, fused, gemm_t, ms, cnt, it_ms):
+    """--full: the roofline entries of the result line, from the in-library kernel timings (ms, cnt
+    of lgx_profile_collect) and the PPO-GEMM event timings (gemm_t) over the timed region, the
+    committed PMC summaries, and the launches timed on their own after it."""
+    import torch
+    N = args.num_envs
+    steps_per_iter = runner.num_steps_per_env
 
     # roofline of the dominant lgx kernel (HIP-event durations over the timed region, DESIGN.md §4-5)
     fused_act = hasattr(env, "_actuator_dvel") and cnt[1] == 0
@@ -573,7 +670,6 @@ def main():
     for r in (roof, roof2):
         if r["achieved"] is not None:
             r["frac"] = r["achieved"] / r["peak"]
-    it_ms = 1000.0 * elapsed / args.steps
     # the PPO-update GEMM instantiations, timed live (events on the launch stream)
     mb_per_iter = runner.alg.num_learning_epochs * runner.alg.num_mini_batches
     gemm_roofs = []
@@ -621,17 +717,7 @@ def main():
         roof["mfma_busy"] = roof["mfma"]["mfma_busy"]
     roof["selection"] = ("largest GPU-time share of the iteration among the physics kernel and the PPO-update GEMM "
                          "families (second-stream launches included)")
-    out = {
-        "metric": (BASELINE_METRIC if (args.task == "go1_rough" and N == 4096)
-                   else f"env-steps/sec (whole node), {args.task} {N} envs/GPU"),
-        "value": value, "unit": "env-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": it_ms, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "fp32", "data": "synthetic (procedural curriculum terrain, random-init policy)",
-        "config": {"workload": WORKLOADS.get(args.task, args.task) +
-                               (", SEA actuator-net torques" if ctrl == "SEA" else "") +
-                               f", PPO {steps_per_iter} steps x {N} envs/GPU, "
-                               f"{runner.alg.num_learning_epochs} epochs x {runner.alg.num_mini_batches} minibatches",
-                   "envs_per_gpu": N, "global_envs": N * world, "parallelism": f"dp{world}"},
+    return {
         "roofline": roof,
         "roofline_others": others,
         "roofline_secondary": roof2,
@@ -639,19 +725,7 @@ def main():
         "dominant_lgx_kernel": roof["kernel"],
         "lgx_kernels": kernels,
         "mfma_utilisation": {k: pmc_mfma_busy(k, args.task, N) for k in MFMA_KERNELS},
-        "last_iteration": runner.last_iteration_stats,
-        "data_parallel": data_parallel,
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        try:
-            out["cpu_baseline"] = cpu_baseline(args.task, args.cpu_envs)
-        except Exception as e:  # reported, never silently replaced
-            out["cpu_baseline"] = {"error": repr(e)}
-    if rank == 0:
-        print(json.dumps(out))
-    if distributed:
-        runner.close()
-        dist.destroy_process_group()
 
 
 if __name__ == "__main__":

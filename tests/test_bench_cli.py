@@ -42,6 +42,19 @@ def test_plain_gpus2_starts_two_ranks_and_propagates_failure():
     assert "local_rank: 0" in r.stderr and "local_rank: 1" in r.stderr
 
 
+def test_full_and_dump_outputs_options(monkeypatch):
+    """--full is off by default (a plain run prints the headline line only) and --dump-outputs
+    takes the directory of the .npy files."""
+    monkeypatch.syspath_prepend(ROOT)
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (3, 2, False, None)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "somewhere"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "somewhere"
+
+
 def _rendezvous(fail_rank=None):
     env = _env(OMP_NUM_THREADS="1")
     if fail_rank is not None:

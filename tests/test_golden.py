@@ -27,7 +27,29 @@ CASES = {"go1_flat": "go1", "go1_rough": "go1_rough", "anymal_c_rough": "anymal_
 
 
 def load(name):
-    return dict(np.load(os.path.join(GOLD, name + ".npz"), allow_pickle=False))
+    """The golden archive `name`: one .npz, or - where that would exceed the size limit for a
+    committed file - its parts <name>.part<k>.npz (tools/golden/parts.py), joined: an array stored
+    in pieces "<key>@@<i>" is their concatenation along axis 0, bit for bit the original."""
+    path = os.path.join(GOLD, name + ".npz")
+    if os.path.exists(path):
+        return dict(np.load(path, allow_pickle=False))
+    k = 0
+    raw = {}
+    while os.path.exists(os.path.join(GOLD, f"{name}.part{k}.npz")):
+        raw.update(np.load(os.path.join(GOLD, f"{name}.part{k}.npz"), allow_pickle=False))
+        k += 1
+    assert raw, f"no golden archive {name}"
+    out, pieces = {}, {}
+    for key, a in raw.items():
+        if "@@" in key:
+            base, i = key.split("@@")
+            pieces.setdefault(base, {})[int(i)] = a
+        else:
+            out[key] = a
+    for base, p in pieces.items():
+        assert sorted(p) == list(range(len(p))), (base, sorted(p))
+        out[base] = np.concatenate([p[i] for i in range(len(p))], axis=0)
+    return out
 
 
 def build(name, g, device="cpu", backend="oracle", overrides=None):

@@ -13,7 +13,7 @@ for native in sys.argv[1:]:
            "--master-addr", "127.0.0.1", "--master-port", str(port()), os.path.join(root, "bench.py"),
            "--gpus", "1", "--steps", os.environ.get("AB_STEPS", "2"), "--warmup", "1",
            "--task", os.environ.get("AB_TASK", "go1_flat_bench"), "--num_envs", os.environ.get("AB_ENVS", "1024"),
-           "--no_cpu_baseline"]
+           "--full", "--no_cpu_baseline"]
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=300)
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     dp = d["data_parallel"]
