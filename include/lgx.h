@@ -491,6 +491,21 @@ int lgx_gae_parts(const float* rewards, const float* values, const uint8_t* done
                   void* stream);
 int lgx_adv_norm(float* advantages, int64_t n, const double* parts, int32_t nparts, void* stream);
 
+/* rsl_rl OnPolicyRunner.learn's episode bookkeeping for one env step, on the device:
+ *   cur_sum += rew; cur_len += 1;
+ *   for every env with dones != 0, in ascending env order:
+ *     append (cur_sum, cur_len) to a ring of `capacity` entries, then zero them.
+ * `count` (device int64) is the number of episodes appended so far.
+ * Entry k of this step lands in slot (count + k) % capacity, and count += K afterwards; when
+ * K > capacity envs finish in one step only the last `capacity` of them are written, so the ring
+ * holds what a deque(maxlen=capacity) holds: its first min(count, capacity) slots are valid and the
+ * oldest entry is slot count % capacity once count >= capacity.  One launch of one workgroup,
+ * deterministic (no atomics; cur_sum is one float32 add per env, as torch's +=).
+ * 0 < capacity <= LGX_EPISODE_RING_MAX. */
+#define LGX_EPISODE_RING_MAX 4096
+int lgx_episode_stats_step(const float* rew, const uint8_t* dones, int64_t num_envs, float* cur_sum, float* cur_len,
+                           float* ring_sum, float* ring_len, int32_t capacity, int64_t* count, void* stream);
+
 /* ---- PPO update (rsl_rl PPO.update, legged_robot_config.py:226-239): the non-GEMM work of a
  * minibatch step.  Activations are net-major [2 (actor, critic), M, H]; the GEMMs between
  * these calls are library GEMMs issued by the host.  All pointers are device pointers. */

@@ -117,3 +117,75 @@ int lgx_launch_gae_norm(const float* rew, const float* val, const uint8_t* dones
   hipLaunchKernelGGL(lgx_adv_norm_kernel, dim3(blocks), dim3(256), 0, stream, adv, n, (const double*)scratch, nparts);
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
+
+// Episode statistics of the runner's collection loop (lgx.h: lgx_episode_stats_step).  ONE
+// workgroup walks the envs in tiles of blockDim.x, twice: the first walk counts the finished envs
+// (K), the second ranks them in env order - the lanes below in the wave's ballot, the waves below
+// in the tile (LDS), the tiles before (a running base every thread carries) - and appends rank r
+// at ring slot (count + r) % capacity.  Only the last `capacity` ranks write, so no two envs of a
+// step meet in one slot and the ring holds what a deque(maxlen=capacity) would after extend().
+// Nothing depends on the order waves run in: no atomics, every output has exactly one writer.
+#define EPS_TPB 1024
+#define EPS_WAVES (EPS_TPB / 64)
+__global__ void __launch_bounds__(EPS_TPB) lgx_episode_stats_kernel(
+    const float* __restrict__ rew, const uint8_t* __restrict__ dones, int64_t n, float* __restrict__ cur_sum,
+    float* __restrict__ cur_len, float* __restrict__ ring_sum, float* __restrict__ ring_len, uint32_t capacity,
+    int64_t* __restrict__ count) {
+  __shared__ uint32_t wave_n[2][EPS_WAVES];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const uint64_t count0 = (uint64_t)*count;   // (read by all before the barriers below, written last by thread 0)
+  uint32_t mine = 0;                          // finished envs of this wave's tiles (wave-uniform)
+  for (int64_t t0 = 0; t0 < n; t0 += EPS_TPB) {
+    const int64_t e = t0 + threadIdx.x;
+    mine += (uint32_t)__popcll(__ballot(e < n && dones[e] != 0));
+  }
+  if (lane == 0) wave_n[0][wave] = mine;
+  __syncthreads();
+  uint64_t K = 0;
+  for (int w = 0; w < EPS_WAVES; ++w) K += wave_n[0][w];
+  const uint64_t first = K > capacity ? K - capacity : 0;   // ranks below it would be pushed out again
+  uint64_t base = 0;                                         // finished envs of the tiles before this one
+  int buf = 1;   // (tile i's wave totals in wave_n[1 - i % 2]: one barrier per tile)
+  for (int64_t t0 = 0; t0 < n; t0 += EPS_TPB, buf ^= 1) {
+    const int64_t e = t0 + threadIdx.x;
+    const bool in = e < n;
+    const bool done = in && dones[e] != 0;
+    const uint64_t mask = __ballot(done);
+    if (lane == 0) wave_n[buf][wave] = (uint32_t)__popcll(mask);
+    __syncthreads();
+    uint32_t below = 0, tile = 0;
+    for (int w = 0; w < EPS_WAVES; ++w) {
+      const uint32_t c = wave_n[buf][w];
+      below += w < wave ? c : 0;
+      tile += c;
+    }
+    if (in) {
+      const float s = cur_sum[e] + rew[e], l = cur_len[e] + 1.f;
+      if (done) {
+        const uint64_t rank = base + below + (uint32_t)__popcll(mask & ((1ull << lane) - 1));
+        if (rank >= first) {
+          const uint32_t slot = (uint32_t)((count0 + rank) % capacity);
+          ring_sum[slot] = s;
+          ring_len[slot] = l;
+        }
+      }
+      cur_sum[e] = done ? 0.f : s;
+      cur_len[e] = done ? 0.f : l;
+    }
+    base += tile;
+  }
+  if (threadIdx.x == 0) *count = (int64_t)(count0 + K);
+}
+
+extern "C" int lgx_episode_stats_step(const float* rew, const uint8_t* dones, int64_t num_envs, float* cur_sum,
+                                      float* cur_len, float* ring_sum, float* ring_len, int32_t capacity,
+                                      int64_t* count, void* stream) {
+  if (!rew || !dones || !cur_sum || !cur_len || !ring_sum || !ring_len || !count)
+    return lgx_fail(LGX_EINVAL, "lgx_episode_stats_step: null argument");
+  if (num_envs <= 0 || capacity <= 0 || capacity > LGX_EPISODE_RING_MAX)
+    return lgx_fail(LGX_EINVAL,
+                    "lgx_episode_stats_step: bad args (num_envs > 0, 0 < capacity <= LGX_EPISODE_RING_MAX)");
+  hipLaunchKernelGGL(lgx_episode_stats_kernel, dim3(1), dim3(EPS_TPB), 0, reinterpret_cast<hipStream_t>(stream), rew,
+                     dones, num_envs, cur_sum, cur_len, ring_sum, ring_len, (uint32_t)capacity, count);
+  return lgx_hip_status("lgx_episode_stats_step");
+}

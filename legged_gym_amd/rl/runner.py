@@ -11,11 +11,11 @@ iteration, fps = num_steps_per_env * num_envs / (collection + learn), as rsl_rl 
 import os
 import statistics
 import time
-from collections import deque
 
 import torch
 
 from .actor_critic import ActorCritic, ActorCriticRecurrent  # noqa: F401  (resolved by name from the cfg)
+from .episode_stats import EpisodeStats
 from .ppo import PPO  # noqa: F401
 
 
@@ -63,10 +63,6 @@ class OnPolicyRunner:
         obs, critic_obs = obs.to(self.device), critic_obs.to(self.device)
         self.alg.actor_critic.train()
         ep_infos = []
-        rewbuffer = deque(maxlen=100)
-        lenbuffer = deque(maxlen=100)
-        cur_reward_sum = torch.zeros(self.env.num_envs, dtype=torch.float, device=self.device)
-        cur_episode_length = torch.zeros(self.env.num_envs, dtype=torch.float, device=self.device)
         # Phase times on CUDA come from stream events read after update(), whose statistics readback
         # already waits for the stream: no extra host synchronisation between the rollout and the
         # update (upstream rsl_rl likewise times with time.time() and no sync).
@@ -76,8 +72,19 @@ class OnPolicyRunner:
         # next rollout has been issued, so the GPU goes from the update straight into that rollout
         # (otherwise it idles ~0.3 ms per iteration while the host returns from the update's
         # synchronisation and issues again).  Same computation, same results.
-        defer = cuda and self.log_dir is None
+        # With a log directory the update is synchronous and the iteration is logged at once.
+        # LGX_DEFER_LOG=1 defers there too: iteration i is logged (same number, same values) once
+        # rollout i + 1 has been issued; an iteration that writes a checkpoint stays synchronous, so
+        # model_<it>.pt holds the parameters it always held.
+        logged = self.log_dir is not None
+        defer_log = cuda and logged and os.environ.get("LGX_DEFER_LOG", "0") == "1"
         pending = prev_end = None
+        # Episode statistics (mean reward / length of the last 100 finished episodes): on CUDA one
+        # lgx_episode_stats_step launch per env step and one readback per iteration, no host
+        # synchronisation during collection; LGX_DEVICE_STATS=0 (and the CPU runner): rsl_rl's
+        # torch / deque block, two blocking gathers per step.  Same lists either way.
+        stats = EpisodeStats(self.env.num_envs, self.device, capacity=100,
+                             kernel=cuda and os.environ.get("LGX_DEVICE_STATS", "1") != "0") if logged else None
         # act -> env.step -> process_env_step: each step's storage-row store rides on the next act's
         # launch (LGX_DEFER_STORE=0: its own launch, as before)
         self.alg.defer_store = os.environ.get("LGX_DEFER_STORE", "1") != "0"
@@ -86,6 +93,7 @@ class OnPolicyRunner:
         try:
             for it in range(self.current_learning_iteration, tot_iter):
                 start = time.time()
+                defer = cuda and (not logged or (defer_log and it % self.save_interval != 0))
                 if cuda:   # (the previous iteration's end event is this one's start: one marker less)
                     ev = [prev_end if prev_end is not None else torch.cuda.Event(enable_timing=True)] + \
                          [torch.cuda.Event(enable_timing=True) for _ in range(2)]
@@ -100,16 +108,11 @@ class OnPolicyRunner:
                         obs, critic_obs = obs.to(self.device), critic_obs.to(self.device)
                         rewards, dones = rewards.to(self.device), dones.to(self.device)
                         self.alg.process_env_step(rewards, dones, infos)
-                        if self.log_dir is not None:
+                        if logged:
                             if "episode" in infos:
                                 ep_infos.append(infos["episode"])
-                            cur_reward_sum += rewards
-                            cur_episode_length += 1
-                            new_ids = (dones > 0).nonzero(as_tuple=False)
-                            rewbuffer.extend(cur_reward_sum[new_ids][:, 0].cpu().numpy().tolist())
-                            lenbuffer.extend(cur_episode_length[new_ids][:, 0].cpu().numpy().tolist())
-                            cur_reward_sum[new_ids] = 0
-                            cur_episode_length[new_ids] = 0
+                            stats.step(rewards, dones)
+                    ticket = stats.request() if logged else None   # (read in log(), after the update)
                     if cuda:
                         ev[1].record()
                     stop = time.time()
@@ -123,7 +126,12 @@ class OnPolicyRunner:
                 if defer:
                     self.alg.update(defer=True)
                     ev[2].record()
-                    pending = ev
+                    pending = (ev, None)
+                    if logged:   # what log() reads from the device, as it is after this update
+                        pending = (ev, dict(it=it, num_learning_iterations=num_learning_iterations, ep_infos=ep_infos,
+                                            stats=stats, ticket=ticket,
+                                            device_values=self._log_values(ep_infos, defer=True)))
+                        ep_infos = []
                     ep_infos.clear()
                     continue
                 mean_value_loss, mean_surrogate_loss = self.alg.update()
@@ -137,8 +145,12 @@ class OnPolicyRunner:
                 self.last_iteration_stats = dict(collection_time=collection_time, learn_time=learn_time,
                                                  value_loss=mean_value_loss, surrogate_loss=mean_surrogate_loss,
                                                  learning_rate=self.alg.learning_rate)
-                if self.log_dir is not None:
-                    self.log(locals())
+                if logged:
+                    rewbuffer, lenbuffer = stats.result(ticket)
+                    self.log(dict(it=it, num_learning_iterations=num_learning_iterations, ep_infos=ep_infos,
+                                  collection_time=collection_time, learn_time=learn_time,
+                                  mean_value_loss=mean_value_loss, mean_surrogate_loss=mean_surrogate_loss,
+                                  rewbuffer=rewbuffer, lenbuffer=lenbuffer))
                     if it % self.save_interval == 0:
                         self.save(os.path.join(self.log_dir, f"model_{it}.pt"))
                 ep_infos.clear()
@@ -155,7 +167,7 @@ class OnPolicyRunner:
             try:
                 self.alg.flush_store()
                 if p is not None:
-                    self._finish_deferred(p)
+                    self._finish_deferred(p, log=completed)
             except Exception:
                 if completed:
                     raise
@@ -164,15 +176,41 @@ class OnPolicyRunner:
         if self.log_dir is not None:
             self.save(os.path.join(self.log_dir, f"model_{self.current_learning_iteration}.pt"))
 
-    def _finish_deferred(self, ev):
+    def _finish_deferred(self, pending, log=True):
         """Statistics of a deferred iteration: losses and learning rate from the update's readback,
-        phase times from its stream events (all complete by the time the next rollout is issued)."""
+        phase times from its stream events (all complete by the time the next rollout is issued);
+        then its log entry (LGX_DEFER_LOG=1)."""
+        ev, locs = pending
         mean_value_loss, mean_surrogate_loss = self.alg.resolve()
         ev[2].synchronize()
         self.last_iteration_stats = dict(collection_time=ev[0].elapsed_time(ev[1]) * 1e-3,
                                          learn_time=ev[1].elapsed_time(ev[2]) * 1e-3,
                                          value_loss=mean_value_loss, surrogate_loss=mean_surrogate_loss,
                                          learning_rate=self.alg.learning_rate)
+        if locs is not None and log:
+            rewbuffer, lenbuffer = locs.pop("stats").result(locs.pop("ticket"))
+            self.log(dict(locs, collection_time=self.last_iteration_stats["collection_time"],
+                          learn_time=self.last_iteration_stats["learn_time"], mean_value_loss=mean_value_loss,
+                          mean_surrogate_loss=mean_surrogate_loss, rewbuffer=rewbuffer, lenbuffer=lenbuffer))
+
+    def _log_values(self, ep_infos, defer=False):
+        """What log() reads from the device, in one reduction and one readback: the mean over the
+        rollout's steps of every extras["episode"] scalar (in key order), then the mean action noise
+        std.  defer=True: (pinned host tensor, event) of a non-blocking copy instead of the list."""
+        with torch.no_grad():
+            vals = self.alg.actor_critic.std.detach().mean().reshape(1)
+            if ep_infos:
+                keys = list(ep_infos[0])
+                steps = torch.stack([torch.as_tensor(ep[key], device=self.device).reshape(())
+                                     for ep in ep_infos for key in keys]).float()
+                vals = torch.cat([steps.view(len(ep_infos), len(keys)).mean(0), vals])
+            if not defer:
+                return vals.tolist()
+            host = torch.empty(vals.shape, dtype=vals.dtype, pin_memory=True)
+            host.copy_(vals, non_blocking=True)
+            event = torch.cuda.Event()
+            event.record()
+            return host, event
 
     def log(self, locs, width=80, pad=35):
         self.tot_timesteps += self.num_steps_per_env * self.env.num_envs
@@ -180,10 +218,15 @@ class OnPolicyRunner:
         it_time = locs["collection_time"] + locs["learn_time"]
         w = self._writer()
         lines = []
+        values = locs.get("device_values")
+        if values is None:
+            values = self._log_values(locs["ep_infos"])
+        elif not isinstance(values, list):
+            values[1].synchronize()
+            values = values[0].tolist()
+        noise_std = values[-1]
         if locs["ep_infos"]:
-            for key in locs["ep_infos"][0]:
-                vals = torch.stack([torch.as_tensor(ep[key], device=self.device).reshape(()) for ep in locs["ep_infos"]])
-                value = vals.mean().item()
+            for key, value in zip(locs["ep_infos"][0], values):
                 if w:
                     w.add_scalar("Episode/" + key, value, locs["it"])
                 lines.append(f"{'Mean episode ' + key + ':':>{pad}} {value:.4f}")
@@ -192,7 +235,7 @@ class OnPolicyRunner:
             w.add_scalar("Loss/value_function", locs["mean_value_loss"], locs["it"])
             w.add_scalar("Loss/surrogate", locs["mean_surrogate_loss"], locs["it"])
             w.add_scalar("Loss/learning_rate", self.alg.learning_rate, locs["it"])
-            w.add_scalar("Policy/mean_noise_std", self.alg.actor_critic.std.mean().item(), locs["it"])
+            w.add_scalar("Policy/mean_noise_std", noise_std, locs["it"])
             w.add_scalar("Perf/total_fps", fps, locs["it"])
             w.add_scalar("Perf/collection time", locs["collection_time"], locs["it"])
             w.add_scalar("Perf/learning_time", locs["learn_time"], locs["it"])
@@ -201,7 +244,7 @@ class OnPolicyRunner:
         s += f"{'Computation:':>{pad}} {fps:.0f} steps/s (collection: {locs['collection_time']:.3f}s, learning {locs['learn_time']:.3f}s)\n"
         s += f"{'Value function loss:':>{pad}} {locs['mean_value_loss']:.4f}\n"
         s += f"{'Surrogate loss:':>{pad}} {locs['mean_surrogate_loss']:.4f}\n"
-        s += f"{'Mean action noise std:':>{pad}} {self.alg.actor_critic.std.mean().item():.2f}\n"
+        s += f"{'Mean action noise std:':>{pad}} {noise_std:.2f}\n"
         if len(locs["rewbuffer"]) > 0:
             s += f"{'Mean reward:':>{pad}} {statistics.mean(locs['rewbuffer']):.2f}\n"
             s += f"{'Mean episode length:':>{pad}} {statistics.mean(locs['lenbuffer']):.2f}\n"

@@ -151,6 +151,7 @@ class LgxCopy2dJob(C.Structure):
 
 PPO_MAX_ACTIONS = 16
 MAX_REDUCE_JOBS = 16
+EPISODE_RING_MAX = 4096   # LGX_EPISODE_RING_MAX: largest ring of lgx_episode_stats_step
 GEMM_PLAIN, GEMM_BIAS_ELU, GEMM_DELU_COLSUM, GEMM_DELU = 0, 1, 2, 3
 GEMM_ALGO_DEFAULT, GEMM_ALGO_F32, GEMM_ALGO_SPLIT_BF16 = 0, 1, 2
 GEMM_TILE_M, GEMM_TILE_N, GEMM_K_STEP = 128, 128, 32   # K step: layer-1 rows padded to 1024 B (aligned 128-B lines)
@@ -246,6 +247,7 @@ def declare(lib, prefix="lgx"):
             "comm_create": (C.c_int, [C.c_char_p, C.POINTER(C.c_uint8), i32, i32, i32, C.POINTER(vp)]),
             "comm_destroy": (C.c_int, [vp]),
             "allreduce_grads": (C.c_int, [vp, vp, C.c_size_t, i32, vp]),
+            "episode_stats_step": (C.c_int, [vp, vp, i64, vp, vp, vp, vp, i32, vp, vp]),
         })
     for name, (res, args) in sigs.items():
         fn = getattr(lib, f"{prefix}_{name}")
@@ -266,7 +268,8 @@ EXPORTED = ["lgx_last_error", "lgx_version", "lgx_physics_lane_split", "lgx_trim
             "lgx_mlp_x3_weight_elems", "lgx_mlp_x3_split", "lgx_mlp_x3_split_layers", "lgx_mlp_x3_lds_bytes", "lgx_mlp_x3_forward", "lgx_mlp_x3_forward_act",
             "lgx_event_create", "lgx_event_destroy", "lgx_event_record", "lgx_stream_wait_event",
             "lgx_launch_bind_event", "lgx_launch_bind_pending",
-            "lgx_comm_unique_id", "lgx_comm_create", "lgx_comm_destroy", "lgx_allreduce_grads"]
+            "lgx_comm_unique_id", "lgx_comm_create", "lgx_comm_destroy", "lgx_allreduce_grads",
+            "lgx_episode_stats_step"]
 
 
 def check_layout(sizes_fn, n=12):

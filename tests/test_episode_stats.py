@@ -1,0 +1,79 @@
+"""CPU: EpisodeStats' torch path and ring readback against rsl_rl's deque block, and the C-ABI
+of lgx_episode_stats_step (header, bindings, exported symbol)."""
+import ctypes as C
+import os
+import re
+
+import torch
+
+from episode_stats_ref import DequeStats, random_sequence
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_cpu_path_reproduces_the_deque_block():
+    from legged_gym_amd.rl.episode_stats import EpisodeStats
+    seq = random_sequence()
+    n = seq[0][0].numel()
+    ref, st = DequeStats(n, "cpu"), EpisodeStats(n, "cpu")
+    assert st.result() == ([], [])
+    for t, (rew, dones) in enumerate(seq):
+        ref.step(rew, dones)
+        st.step(rew, dones)
+        st.request()
+        assert torch.equal(st.cur_sum, ref.cur_reward_sum) and torch.equal(st.cur_len, ref.cur_episode_length), t
+        assert st.result() == ref.lists(), t
+    assert len(ref.rewbuffer) == 100
+
+
+def test_result_reads_the_ring_oldest_first():
+    """The ring layout the kernel writes: entry k of the run in slot k % capacity; the first
+    min(count, capacity) slots valid; the oldest at count % capacity once the ring is full."""
+    from legged_gym_amd.rl.episode_stats import EpisodeStats
+    cap = 7
+    for count in (0, 3, 7, 8, 12, 2 ** 31 + 5):
+        st = EpisodeStats(4, "cpu", capacity=cap)
+        ref = DequeStats(4, "cpu", capacity=cap)
+        first = max(0, count - 2 * cap)      # (earlier entries are long pushed out)
+        for k in range(first, count):
+            st.rings[0, k % cap] = float(k % 1000)
+            st.rings[1, k % cap] = float(k % 1000 + 1)
+            ref.rewbuffer.append(float(k % 1000))
+            ref.lenbuffer.append(float(k % 1000 + 1))
+        st.count[0] = count
+        st.request()
+        assert st.result() == ref.lists(), count
+
+
+def test_two_requests_may_be_outstanding():
+    from legged_gym_amd.rl.episode_stats import EpisodeStats
+    st = EpisodeStats(3, "cpu")
+    one = torch.ones(3)
+    st.step(one, torch.tensor([True, False, False]))
+    a = st.request()
+    st.step(one, torch.tensor([False, True, False]))
+    b = st.request()
+    assert st.result(a) == ([1.0], [1.0])
+    assert st.result(b) == ([1.0, 2.0], [1.0, 2.0]) and st.result() == st.result(b)
+
+
+def test_header_and_bindings_declare_the_entry_point():
+    from legged_gym_amd.sim import abi
+    txt = open(os.path.join(ROOT, "include", "lgx.h")).read()
+    assert re.search(r"\bint\s+lgx_episode_stats_step\s*\(", txt)
+    m = re.search(r"#define\s+LGX_EPISODE_RING_MAX\s+(\d+)", txt)
+    assert m and int(m.group(1)) == abi.EPISODE_RING_MAX >= 128
+    assert "lgx_episode_stats_step" in abi.EXPORTED
+
+
+def test_library_exports_the_entry_point():
+    path = os.path.join(ROOT, "legged_gym_amd", "liblgx.so")
+    assert os.path.exists(path), "run __graft_entry__.build() first"
+    import torch  # noqa: F401  (HIP runtime first)
+    from legged_gym_amd.sim import abi
+    lib = abi.declare(C.CDLL(path))
+    fn = lib.lgx_episode_stats_step
+    assert fn.restype is C.c_int and len(fn.argtypes) == 10
+    # the argument checks precede any device call
+    assert fn(None, None, 4, None, None, None, None, 100, None, None) == -1
+    assert b"lgx_episode_stats_step" in lib.lgx_last_error()

@@ -1,0 +1,81 @@
+"""Wall time per training iteration of OnPolicyRunner.learn as scripts/train.py runs it (with a log
+directory) and as bench.py runs it (without): go1_rough, 4096 envs.
+
+    python tools/train_time.py [--configs logged,logged_old,logged_defer,unlogged] [--iters 50]
+                               [--warmup 10] [--windows 5]
+
+Configurations (one runner with a temporary log directory, one without, on one env):
+    logged        log directory, device episode statistics (the default path)
+    logged_old    log directory, LGX_DEVICE_STATS=0 (rsl_rl's torch / deque block)
+    logged_defer  log directory, LGX_DEFER_LOG=1
+    unlogged      no log directory
+A window is one learn(iters) between two device synchronisations, its stdout discarded; with a
+log directory it contains the checkpoints learn() writes (every save_interval iterations and at
+its end).  The windows of the configurations alternate, after learn(warmup) of each.  Prints one
+JSON line: per configuration the median ms per iteration and every window's.
+"""
+import argparse
+import contextlib
+import json
+import os
+import statistics
+import sys
+import tempfile
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch  # noqa: E402
+
+import legged_gym_amd.envs  # noqa: E402,F401
+from legged_gym_amd.utils.helpers import get_args  # noqa: E402
+from legged_gym_amd.utils.task_registry import task_registry  # noqa: E402
+
+ENV = {"logged": {}, "logged_old": {"LGX_DEVICE_STATS": "0"}, "logged_defer": {"LGX_DEFER_LOG": "1"}, "unlogged": {}}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--configs", default="logged,logged_old,logged_defer,unlogged")
+    ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--windows", type=int, default=5)
+    ap.add_argument("--num_envs", type=int, default=4096)
+    a = ap.parse_args()
+    configs = a.configs.split(",")
+    assert all(c in ENV for c in configs), f"configurations: {sorted(ENV)}"
+    assert torch.cuda.is_available(), "train_time.py measures on the GPU"
+    task = "go1_rough"
+    env_cfg, train_cfg = task_registry.get_cfgs(task)
+    env_cfg.env.num_envs = a.num_envs
+    cli = get_args(["--sim_device", "cuda:0", "--rl_device", "cuda:0", "--headless", "--task", task])
+    out = {c: [] for c in configs}
+    with tempfile.TemporaryDirectory() as tmp, open(os.devnull, "w") as null, contextlib.redirect_stdout(null):
+        env, _ = task_registry.make_env(task, args=cli, env_cfg=env_cfg)
+        runners = {}
+        for logged in sorted({c != "unlogged" for c in configs}):
+            runners[logged], _ = task_registry.make_alg_runner(env, name=task, args=cli, train_cfg=train_cfg,
+                                                               log_root=tmp if logged else None)
+
+        def learn(config, n):
+            for k in ("LGX_DEVICE_STATS", "LGX_DEFER_LOG"):
+                os.environ.pop(k, None)
+            os.environ.update(ENV[config])
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            runners[config != "unlogged"].learn(n)
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) / n * 1e3
+
+        for c in configs:
+            learn(c, a.warmup)
+        for _ in range(a.windows):
+            for c in configs:
+                out[c].append(round(learn(c, a.iters), 4))
+    print(json.dumps({"task": task, "num_envs": a.num_envs, "iters_per_window": a.iters, "warmup_iters": a.warmup,
+                      "device": torch.cuda.get_device_name(0),
+                      "ms_per_iteration": {c: {"median": round(statistics.median(w), 4), "windows": w}
+                                           for c, w in out.items()}}), flush=True)
+
+
+if __name__ == "__main__":
+    main()
