@@ -1,23 +1,25 @@
 """The PPO update of rsl_rl v1.0.x (`PPO.update`; legged_robot_config.py:226-239) as an explicit
 forward/backward over flat parameter/gradient buffers — no autograd graph, no per-op launches.
 
-Per minibatch (M rows), on one stream, no host synchronisation:
-  weight preparation (lgx_copy2d: zero-padded layer-1 weights, transposed hidden weights) on the
-  first minibatch of an update; afterwards the Adam step writes these copies (lgx_adam_clip_mirror)
-  gather obs rows (lgx_ppo_gather_rows_padded, K padded to a multiple of 16)
-  hidden layers: lgx_gemm_nt with the bias + ELU epilogue, {actor, critic} batched in one launch
-                 (LGX_PPO_GEMM=auto: library GEMM + lgx_bias_act for layers 2..L)
-  heads + loss: lgx_ppo_loss = output layers (in-kernel dot products), log-prob / ratio / clipped surrogate / clipped value loss / entropy
-         / KL and the analytic gradient w.r.t. mu, value, std, head biases; its finalize applies the
-         device-side adaptive schedule (data-parallel: lgx_ppo_adapt_lr after the gradient
-         all-reduce the KL rides in)
-  backward: lgx_head_bwd, then per layer split-K bmm for dW, lgx_gemm_nt for dA with the ELU'
-            + bias-gradient column-sum epilogue
+Per minibatch (M rows), no host synchronisation (the stages of `_minibatch_body`):
+  inputs: the weight copies of the GEMMs (bf16 limbs / padded, transposed f32) prepared on an
+          update's first minibatch, afterwards kept current by the Adam step; the layer-1 input
+          rows gathered with K padded to a multiple of abi.GEMM_K_STEP = 32 (once per update)
+  forward: lgx_gemm_nt with the bias + ELU epilogue, {actor, critic} batched in one launch
+  loss / heads: lgx_ppo_loss_bwd = output layers, log-prob / ratio / clipped surrogate / clipped
+          value loss / entropy / KL, the analytic gradient w.r.t. mu, value, std, head biases and
+          the output-layer backward; its finalize (in the reduction launch) applies the device-side
+          adaptive schedule (data-parallel: lgx_ppo_adapt_lr after the all-reduce the KL rides in)
+  backward: per layer lgx_gemm_tn for dW (split-K, on a second stream) next to lgx_gemm_nt for dA
+          with the ELU' epilogue; the bias gradients are column sums from either
+  reductions: lgx_reduce_slices*: all split-K and bias partials -> flat gradient
+          [data-parallel: the flat gradient + the minibatch KL all-reduced over RCCL, two buckets]
+  optimizer step: lgx_adam_clip*: clip_grad_norm_(max_grad_norm) + Adam on the flat buffers
   (hidden widths that are not multiples of 128, or LGX_PPO_GEMM=lib: library GEMMs through torch
-   + lgx_bias_act / lgx_elu_bwd_colsum instead of lgx_gemm_nt)
-  lgx_reduce_slices: all split-K and bias partials -> flat gradient (one launch)
-  [ONE all-reduce over RCCL when data-parallel: flat gradient + the minibatch KL]
-  lgx_adam_clip[_mirror]: clip_grad_norm_(max_grad_norm) + Adam on the flat buffers (+ the GEMM weight copies)
+   + lgx_bias_act / lgx_elu_bwd_colsum instead of lgx_gemm_nt / lgx_gemm_tn)
+Which of these launches a configuration issues is decided in three places: `_switches` reads the
+environment, `_policy_plan` takes the policy apart (supported() and __init__ share it), `_alloc`
+builds the launch plan for a minibatch size.
 The module's nn.Parameters become views of the flat buffer, so state_dict / load_state_dict /
 the rollout's fused inference see the updated weights; the optimizer is `FlatAdam`, whose
 state_dict has torch.optim.Adam's format (checkpoints stay loadable by upstream tooling).
@@ -25,11 +27,44 @@ state_dict has torch.optim.Adam's format (checkpoints stay loadable by upstream 
 import ctypes as C
 import os
 import time
+from types import SimpleNamespace
 
 import torch
 import torch.nn as nn
 
 from legged_gym_amd.sim import abi
+
+
+def _switches():
+    """The update's environment switches (DESIGN.md 4.5 has the table): the module's only reader
+    of os.environ.  Plan switches are taken when the launch plan is built (supported() / __init__,
+    or _alloc for a new minibatch size); run switches at the start of every update() /
+    gradients() call, for all of its minibatches."""
+    env = os.environ.get
+
+    def on(name):
+        return env(name, "1") != "0"
+    return SimpleNamespace(
+        # plan
+        gemm=env("LGX_PPO_GEMM", "lgx"),                  # "lgx" | "auto" | "lib"
+        split=env("LGX_GEMM_ALGO", "split") != "f32",
+        dw_lgx=env("LGX_PPO_DW", "lgx") != "lib",
+        splits=env("LGX_PPO_SPLITS"),                     # "s1,s2,..." per layer
+        head_in_loss=on("LGX_PPO_HEAD_IN_LOSS"),
+        loss_bwd=on("LGX_PPO_LOSS_BWD"),
+        tn_colsum=on("LGX_PPO_TN_COLSUM"),
+        fused_sq=on("LGX_PPO_FUSED_SQ"),
+        fused_recurrent=on("LGX_PPO_FUSED_RECURRENT"),
+        # plan (the dW slices' CU fill) and run (dW on the side stream)
+        dw_side=on("LGX_PPO_DW_SIDE"),
+        # run
+        early_reduce=on("LGX_PPO_EARLY_REDUCE"),
+        dev_events=on("LGX_PPO_DEV_EVENTS"),
+        bind=on("LGX_PPO_BIND"),
+        dw1_batched=on("LGX_PPO_DW1_BATCHED"),
+        # process-wide
+        tuned_gemms=on("LGX_TUNED_GEMMS"),
+        native_allreduce=env("LGX_NATIVE_ALLREDUCE", "0") == "1")
 
 
 class _TunedGemms:
@@ -44,7 +79,7 @@ class _TunedGemms:
 
     def __init__(self):
         self.ok = False
-        if os.environ.get("LGX_TUNED_GEMMS", "1") == "0":
+        if not _switches().tuned_gemms:
             return
         import torch.cuda.tunable as tunable
         from legged_gym_amd import LEGGED_GYM_ROOT_DIR
@@ -146,40 +181,72 @@ class FlatAdam:
         self.step_dev.fill_(step)
 
 
+def _policy_plan(ac, sw):
+    """The policy taken apart for the update, under the plan switches `sw`: the linear layers of
+    actor and critic, the hidden widths and which GEMM paths drive them - or None for a policy
+    that __init__ + _alloc cannot drive (supported() is exactly this test)."""
+    recurrent = bool(getattr(ac, "is_recurrent", False))
+    if recurrent and not (sw.fused_recurrent and hasattr(ac, "memory_a") and hasattr(ac, "memory_c")):
+        return None   # (LGX_PPO_FUSED_RECURRENT=0: recurrent policies on the autograd update)
+    try:
+        nets = [list(ac.actor), list(ac.critic)]
+    except AttributeError:
+        return None
+    (la, aa), (lc, acr) = (([m for m in net if isinstance(m, nn.Linear)],
+                            [m for m in net if not isinstance(m, nn.Linear)]) for net in nets)
+    if not all(isinstance(m, nn.ELU) and m.alpha == 1.0 for m in aa + acr):
+        return None
+    if len(la) != len(lc) or len(la) < 2 or len(aa) != len(la) - 1 or len(acr) != len(lc) - 1:
+        return None
+    hidden = [l.out_features for l in la[:-1]]
+    L = len(hidden)
+    # one lgx_reduce_slices launch takes every gradient block: dW1 (x2 with a privileged critic
+    # of another width), dW_2..L, the head dW, and the bias sums of every hidden layer; the
+    # weight copies the Adam step maintains: padded W1 (x2) + transposed W_2..L
+    sep = la[0].in_features != lc[0].in_features
+    jobs = 2 * L + 1 + int(sep)
+    mirrors = 2 * L - 1 + int(sep)     # split-bf16 limb copies: W_1 (x2), W_k and W_k^T
+    if not (hidden == [l.out_features for l in lc[:-1]] and all(hk % 4 == 0 for hk in hidden) and hidden[-1] <= 1024
+            and lc[-1].out_features == 1 and la[-1].out_features <= abi.PPO_MAX_ACTIONS and ac.std.dim() == 1
+            and jobs <= abi.MAX_REDUCE_JOBS and mirrors <= abi.MAX_REDUCE_JOBS):
+        return None
+    # lgx_gemm: the hidden layers on lgx_gemm_nt (LGX_PPO_GEMM "lgx": every forward and dA; "auto":
+    # the layer-1 forward and the dA products, library GEMM + lgx_bias_act for the other forwards),
+    # else ("lib", or widths off the GEMM's N tile) library GEMMs.  split: its split-bf16 products
+    # with pre-split weights, else exact-f32 MFMA with f32 weight copies.  tn: the weight gradients
+    # on lgx_gemm_tn (split-bf16 only), else library f32 bmm over row slices
+    lgx_gemm = all(hk % abi.GEMM_TILE_N == 0 for hk in hidden) and sw.gemm != "lib"
+    if recurrent and not lgx_gemm:
+        return None   # (the memories' outputs enter through the padded rows of the lgx_gemm plan only)
+    return SimpleNamespace(la=la, lc=lc, hidden=hidden, recurrent=recurrent, lgx_gemm=lgx_gemm,
+                           lgx_fwd_layers=set(range(L)) if sw.gemm == "lgx" else {0}, split=sw.split,
+                           tn=lgx_gemm and sw.split and sw.dw_lgx)
+
+
+_UNTRIED = object()   # FusedPPOUpdate._comm before _lgx_comm() has run
+
+
 class FusedPPOUpdate:
     """Drives the lgx PPO kernels for a standard rsl_rl ActorCritic (identical ELU hidden stacks
     for actor and critic)."""
 
     SPLITS = 8
 
+    # state created on first use (None / empty until then)
+    run = None                                   # the run switches of the current update() / gradients() call
+    _side = _ev_in = _ev_out = None              # the backward's second stream and its torch join events
+    _dev_ev = _armed = None                      # device join events; the slot bound to the next launch
+    _perm_stream = None
+    _pin_stats = _pin_lr = _pin_ev = None        # a deferred update's readback
+    _comm, _comm_last = _UNTRIED, None           # lgx_comm (None: the torch path); its last collective
+    _t_period = _t_count = _t_mb = 0             # time_gemms()
+    _t_events = _c_events = ()
+    Xall = Xall2 = Xcall = None                  # _gather_all's buffers
+    _rec_idx = _mem_ctx = None                   # recurrent minibatches
+
     @staticmethod
     def supported(ac):
-        def lin(seq):
-            return [m for m in seq if isinstance(m, nn.Linear)], [m for m in seq if not isinstance(m, nn.Linear)]
-        if getattr(ac, "is_recurrent", False) and (os.environ.get("LGX_PPO_FUSED_RECURRENT", "1") == "0"
-                                                   or not hasattr(ac, "memory_a") or not hasattr(ac, "memory_c")):
-            return False   # (LGX_PPO_FUSED_RECURRENT=0: recurrent policies on the autograd update)
-        try:
-            la, aa = lin(ac.actor)
-            lc, acr = lin(ac.critic)
-        except AttributeError:
-            return False
-        if not all(isinstance(m, nn.ELU) and m.alpha == 1.0 for m in aa + acr):
-            return False
-        if len(la) != len(lc) or len(la) < 2 or len(aa) != len(la) - 1 or len(acr) != len(lc) - 1:
-            return False
-        ha = [l.out_features for l in la[:-1]]
-        hc = [l.out_features for l in lc[:-1]]
-        L = len(ha)
-        # one lgx_reduce_slices launch takes every gradient block: dW1 (x2 with a privileged critic
-        # of another width), dW_2..L, the head dW, and the bias sums of every hidden layer; the
-        # weight copies the Adam step maintains: padded W1 (x2) + transposed W_2..L
-        sep = la[0].in_features != lc[0].in_features
-        jobs = 2 * L + 1 + int(sep)
-        mirrors = 2 * L - 1 + int(sep)     # split-bf16 limb copies: W_1 (x2), W_k and W_k^T
-        return (ha == hc and all(h % 4 == 0 for h in ha) and ha[-1] <= 1024 and lc[-1].out_features == 1
-                and la[-1].out_features <= abi.PPO_MAX_ACTIONS and ac.std.dim() == 1
-                and jobs <= abi.MAX_REDUCE_JOBS and mirrors <= abi.MAX_REDUCE_JOBS)
+        return _policy_plan(ac, _switches()) is not None
 
     def __init__(self, ppo):
         from legged_gym_amd.sim import lib as lgxlib
@@ -189,10 +256,13 @@ class FusedPPOUpdate:
         self.ppo = ppo
         ac = ppo.actor_critic
         self.dev = next(ac.parameters()).device
-        la = [m for m in ac.actor if isinstance(m, nn.Linear)]
-        lc = [m for m in ac.critic if isinstance(m, nn.Linear)]
+        plan = _policy_plan(ac, _switches())
+        if plan is None:
+            raise ValueError("FusedPPOUpdate.supported(actor_critic) is False for this policy")
+        la, lc = plan.la, plan.lc
+        self.hidden, self.recurrent = plan.hidden, plan.recurrent
+        self.lgx_gemm, self.lgx_fwd_layers, self.split, self.tn = plan.lgx_gemm, plan.lgx_fwd_layers, plan.split, plan.tn
         self.L = len(la) - 1                       # hidden layers
-        self.hidden = [l.out_features for l in la[:-1]]
         self.num_obs = la[0].in_features
         self.num_cobs = lc[0].in_features
         self.A = la[-1].out_features
@@ -209,7 +279,6 @@ class FusedPPOUpdate:
         # recurrent policies (ActorCriticRecurrent): the memories' parameters after the heads' (their
         # gradients come from torch autograd through the LSTM / GRU, fed with the heads' input
         # gradient dX = dZ_1 W_1 of the fused backward; the clip norm and Adam cover them too)
-        self.recurrent = bool(getattr(ac, "is_recurrent", False))
         self.mem_params = (list(ac.memory_a.parameters()) + list(ac.memory_c.parameters())) if self.recurrent else []
         order += self.mem_params
         n = sum(p.numel() for p in order)
@@ -247,21 +316,8 @@ class FusedPPOUpdate:
         self.std_off = self.off[id(ac.std)]
         params = list(ac.parameters())
         self.optimizer = FlatAdam(params, self.flat_p, self.flat_g, ppo.learning_rate)
-        import os
-        # LGX_PPO_GEMM: "lgx" (default) = every hidden-layer forward and backward dA on lgx_gemm_nt
-        # (epilogues fused; measured ~1 % faster per iteration on MI355X than "auto"); "auto" =
-        # lgx_gemm_nt for the layer-1 forward and the dA products, library GEMM + lgx_bias_act for
-        # the other forwards; "lib" = none
-        mode = os.environ.get("LGX_PPO_GEMM", "lgx")
-        self.lgx_gemm = all(hk % abi.GEMM_TILE_N == 0 for hk in self.hidden) and mode != "lib"
-        self.lgx_fwd_layers = set(range(self.L)) if mode == "lgx" else {0}
-        # LGX_GEMM_ALGO: "split" (default) = lgx_gemm_nt's split-bf16 products (f32-accurate, bf16
-        # MFMA) with pre-split weights; "f32" = the exact-f32 MFMA path with f32 weight copies
-        self.split = os.environ.get("LGX_GEMM_ALGO", "split") != "f32"
-        # LGX_PPO_DW: "lgx" (default with split-bf16 GEMMs) = weight gradients on lgx_gemm_tn
-        # (split-bf16, transposed LDS reads); "lib" = library f32 bmm over row slices
-        self.tn = self.lgx_gemm and self.split and os.environ.get("LGX_PPO_DW", "lgx") != "lib"
         self.gemm_dw = {}   # layer -> lgx_gemm_tn argument blocks (filled by _build_gemm_plan)
+        self.colsum = {}    # layer -> dW's column-sum partials (the bias gradient; _build_gemm_plan)
         self.norm_parts = torch.zeros(256, device=self.dev)
         self._mirrors_valid = False
         self.stats = torch.zeros(3, device=self.dev)
@@ -270,19 +326,20 @@ class FusedPPOUpdate:
 
     # ------------------------------------------------------------------ buffers
     def _alloc(self, M):
+        """Buffers and the launch plan for minibatches of M rows, under the plan switches read
+        here (kept until M changes)."""
         if self.M == M:
             return
         dev, h, A = self.dev, self.hidden, self.A
+        sw = _switches()
         self.M = M
         # split-K row slices of each layer's dW GEMM (library bmm over slices, partials reduced in
-        # lgx_reduce_slices): enough output tiles to fill the CUs. LGX_PPO_SPLITS="s1,s2,..." per layer
-        env = os.environ.get("LGX_PPO_SPLITS")
-        want = [int(x) for x in env.split(",")] if env else []
+        # lgx_reduce_slices): enough output tiles to fill the CUs (half of them when dW runs on the
+        # side stream next to the dA GEMMs). LGX_PPO_SPLITS="s1,s2,..." per layer
+        want = [int(x) for x in sw.splits.split(",")] if sw.splits else []
+        fill = 0.5 if sw.dw_side else 1.0
         self.Sk = []
         for k in range(self.L):
-            # (dW on the side stream, next to the dA GEMMs: tiles for half the CUs - measured 10.32
-            # -> 10.20 ms per update against a full CU round of tiles)
-            fill = 0.5 if os.environ.get("LGX_PPO_DW_SIDE", "1") != "0" else 1.0
             sk = want[k] if k < len(want) else (self._tn_slices(h[k], h[k - 1] if k else self.num_obs, M, fill=fill)
                                                 if self.tn else self.SPLITS)
             self.Sk.append(sk if sk > 0 and M % sk == 0 else 1)
@@ -316,25 +373,25 @@ class FusedPPOUpdate:
         # with them, loss + output-layer backward in one launch (lgx_ppo_loss_bwd, its loss finalize
         # in the reduction launch) unless LGX_PPO_LOSS_BWD=0
         H = h[-1]
-        self.head_in_loss = (os.environ.get("LGX_PPO_HEAD_IN_LOSS", "1") != "0" and H % 16 == 0
-                             and (A + 1) * H * 4 <= 65536)
+        self.head_in_loss = sw.head_in_loss and H % 16 == 0 and (A + 1) * H * 4 <= 65536
         lay = (C.c_int64 * 3)()
         self.check(self.lib.lgx_ppo_loss_bwd_layout(M, A, H, lay), "loss_bwd_layout")
-        self.loss_bwd = self.head_in_loss and lay[2] <= 96 * 1024 and os.environ.get("LGX_PPO_LOSS_BWD", "1") != "0"
+        self.loss_bwd = self.head_in_loss and lay[2] <= 96 * 1024 and sw.loss_bwd
         if self.loss_bwd:
             self.loss_parts = torch.empty(int(lay[0]), device=dev)
             self.head_parts = torch.empty(int(lay[1]), device=dev)
         else:
             self.loss_parts = torch.empty(int(self.lib.lgx_ppo_loss_partials_floats(M, A)), device=dev)
             self.head_parts = torch.empty(int(self.lib.lgx_head_bwd_partials_floats(M, A, H)), device=dev)
+        self.gemm_dw, self.colsum = {}, {}
         if self.lgx_gemm:
             self.col_parts = [torch.empty(int(self.lib.lgx_gemm_partials_floats(M, hk, 2)), device=dev)
                               for hk in h[:-1]]
-            self._build_gemm_plan()
+            self._build_gemm_plan(sw)
         else:
             self.col_parts = [torch.empty(int(self.lib.lgx_colsum_partials_floats(M, hk, 2)), device=dev)
                               for hk in h[:-1]]
-        self._build_reduce_jobs()
+        self._build_reduce_jobs(sw)
 
     @staticmethod
     def _tn_slices(R, Cc, M, cus=256, fill=1.0):
@@ -349,7 +406,7 @@ class FusedPPOUpdate:
             s //= 2
         return s
 
-    def _build_gemm_plan(self):
+    def _build_gemm_plan(self, sw):
         """Fixed argument blocks of every lgx_gemm_nt / lgx_copy2d launch of a minibatch (the
         buffers do not move, so a minibatch issues the prepared structs)."""
         M, h, L, dev = self.M, self.hidden, self.L, self.dev
@@ -358,12 +415,12 @@ class FusedPPOUpdate:
         shared = self.Xcp is None and self.num_obs == self.num_cobs
         copies = []
 
-        def copy(src_ptr, dst, rows, cols, batch, transpose, src_ld, dst_ld):
+        def copy(src_ptr, dst, rows, cols, batch, transpose, src_ld, dst_ld, limbs=0):
             j = abi.LgxCopy2dJob()
             j.src, j.dst = src_ptr, dst.data_ptr()
             j.src_ld, j.src_bs = src_ld, rows * cols
             j.dst_ld, j.dst_bs = dst_ld, (cols if transpose else rows) * dst_ld
-            j.rows, j.cols, j.batch, j.transpose = rows, cols, batch, int(transpose)
+            j.rows, j.cols, j.batch, j.transpose = rows, cols, batch, int(transpose) | limbs
             copies.append(j)
         w1 = fp.data_ptr() + f4 * self.Wg[0]
         nl = [None] * (L + 1)   # split-bf16: limb copies of W_1 / W_k (forward) and W_k^T (backward dA)
@@ -375,11 +432,7 @@ class FusedPPOUpdate:
                 nout, kout = (cols, rows) if transpose else (rows, cols)
                 ld = int(self.lib.lgx_split_bf16_elems(1, kout))
                 buf = torch.zeros(batch * nout * ld, dtype=torch.int16, device=dev)
-                j = abi.LgxCopy2dJob()
-                j.src, j.dst = src_ptr, buf.data_ptr()
-                j.src_ld, j.src_bs, j.dst_ld, j.dst_bs = cols, rows * cols, ld, nout * ld
-                j.rows, j.cols, j.batch, j.transpose = rows, cols, batch, int(transpose) | 2
-                copies.append(j)
+                copy(src_ptr, buf, rows, cols, batch, transpose, cols, ld, limbs=2)
                 return buf
             if shared:
                 nl[0] = (limbs(w1, h[0], self.num_obs, 2, False),)
@@ -424,7 +477,6 @@ class FusedPPOUpdate:
             return g
         fwd = [[]]
         b0 = fp.data_ptr() + f4 * self.bo[0]
-        self.fwd0_src = ["x"] if shared else ["x", "xc"]
         w1p = None if self.split else self.W1p.data_ptr()
         if shared:   # one input for both networks: batch stride 0
             fwd[0].append(gemm(self.Xp.data_ptr(), self.Kp, 0, w1p, self.Kp, h[0] * self.Kp, self.Y[0],
@@ -444,7 +496,6 @@ class FusedPPOUpdate:
         # algorithmic K of each launch (layer 1: the unpadded input width) for the bench's roofline
         self.k_alg = {id(g): k for g, k in zip(fwd[0], [self.num_obs, self.num_cobs])}
         # weight gradients (lgx_gemm_tn): dW_k = dZ_k^T Y_{k-1} over Sk row slices into P[k]
-        self.gemm_dw = {}
         if self.tn:
             def tn(A, lda, sa, B, ldb, sb, Cp, R, Cc, S, batch):
                 t = abi.LgxGemmTnArgs()
@@ -475,11 +526,9 @@ class FusedPPOUpdate:
                                           self.num_obs, self.Sk[0], 2)]
         # bias gradients db_k of the hidden layers below the last: the column sums of dZ_k, taken by
         # dW_k's lgx_gemm_tn from the rows it stages anyway (per-slice partials, reduced with the
-        # weight gradients); the dA GEMM producing dZ_k then runs the plain ELU' epilogue
-        # (LGX_GEMM_DELU: transposed accumulators, output deferred into the next tile's slots).
+        # weight gradients); the dA GEMM producing dZ_k then runs the plain ELU' epilogue.
         # Layers whose dW is not on lgx_gemm_tn keep the ELU' + column-sum epilogue.
-        self.colsum = {}
-        if self.split and os.environ.get("LGX_PPO_TN_COLSUM", "1") != "0":
+        if self.split and sw.tn_colsum:
             for k in range(L - 1):
                 if k not in self.gemm_dw:
                     continue
@@ -503,7 +552,7 @@ class FusedPPOUpdate:
         st = self.ppo.storage
         return st is not None and st.privileged_observations is not None
 
-    def _build_reduce_jobs(self):
+    def _build_reduce_jobs(self, sw):
         M, S, h, A = self.M, self.S, self.hidden, self.A
         g = self.flat_g
         jobs = []
@@ -523,16 +572,14 @@ class FusedPPOUpdate:
             job(self.P[0][1], self.Wg[0] + n1, n1c, 1, 0, Sk[0], n1c, 0)
         else:
             job(self.P[0], self.Wg[0], n1, 2, Sk[0] * n1, Sk[0], n1, n1)            # dW1 (actor, critic)
-        colsum = getattr(self, "colsum", {})
+        colsum = self.colsum
         if 0 in colsum:   # db_1 from dW1's column sums: complete with dW1
             job(colsum[0], self.bo[0], h[0], 2, Sk[0] * h[0], Sk[0], h[0], h[0])
         elif self.L > 1:
-            # db_1 from the dA_1 GEMM's ELU' + column-sum partials (dW1 not on lgx_gemm_tn: e.g. 48 or
-            # 169 observations, whose padded rows are narrower than dW1's 128-column tiles).  dA_1 runs
-            # on the main stream after the side stream's last join, so this job belongs with dW1's on
-            # the main stream: reduced after dA_1, and inside the [0, nW1) all-reduce bucket that is
-            # issued from the main stream (in the side stream's early reduction it would read the
-            # partials before dA_1 wrote them)
+            # db_1 from the dA_1 GEMM's ELU' + column-sum partials (dW1 not on lgx_gemm_tn: e.g. 48
+            # observations, whose padded rows are narrower than dW1's 128-column tiles).  dA_1 runs on
+            # the main stream after the side stream's last join, so this job goes with dW1's: in the
+            # side stream's early reduction it would read the partials before dA_1 wrote them
             cchunks = self.col_parts[0].numel() // (2 * h[0])
             job(self.col_parts[0], self.bo[0], 2 * h[0], 1, 0, cchunks, 2 * h[0], 0)
         n_dw1 = len(jobs)   # (the layer-1 jobs come first: the rest can be reduced before dW1 is done)
@@ -557,15 +604,12 @@ class FusedPPOUpdate:
         self.jobs_dw1 = (abi.LgxReduceJob * n_dw1)(*jobs[:n_dw1])
         self.jobs_rest = (abi.LgxReduceJob * (len(jobs) - n_dw1))(*jobs[n_dw1:])
         # every input of jobs_rest comes from the side stream's dW launches (partials, column sums)
-        # or from launches on the main stream before the side stream's first join (loss): the
-        # early reduction then needs no join after the dA GEMMs.  (db_k from a dA epilogue, k >= 2,
-        # is written on the main stream after a join: then the join is needed; db_1 is never in
-        # jobs_rest.)
+        # or from the main stream before the side stream's first join (loss): the early reduction
+        # then needs no join after the dA GEMMs (a db_k from a dA epilogue, k >= 2, needs it)
         self.rest_on_side = all(k in colsum for k in range(1, self.L - 1))
         # the clip norm's sums of squares written by the reduction launches themselves
-        # (lgx_reduce_slices_sq; single-process updates with the fused loss): one launch less per minibatch
-        self.fused_sq = (self.lgx_gemm and self.loss_bwd and not self.recurrent
-                         and os.environ.get("LGX_PPO_FUSED_SQ", "1") != "0")
+        # (lgx_reduce_slices_sq; single-process updates with the fused loss)
+        self.fused_sq = self.lgx_gemm and self.loss_bwd and not self.recurrent and sw.fused_sq
         if self.fused_sq:
             blocks = self.lib.lgx_reduce_slices_blocks
             self.nsq_rest = int(blocks(self.jobs_rest, len(self.jobs_rest), 1)) if len(self.jobs_rest) else 0
@@ -582,67 +626,74 @@ class FusedPPOUpdate:
         reading the statistics and the adapted learning rate back (one host synchronisation).
         defer=True returns None right after issuing: the readback goes to pinned host memory behind
         an event and resolve() - called by the next update() or by the caller - applies it, so the
-        host can issue the next rollout while this update still runs (the GPU otherwise idles at the
-        iteration boundary until the host returns from the synchronisation and issues again)."""
+        host can issue the next rollout while this update still runs."""
         self.resolve()   # (a previous deferred update finished long before this one is issued)
         if self.recurrent:
             return self._update_recurrent(defer)
         t_issue = time.perf_counter()
         ppo = self.ppo
-        st = ppo.storage
-        T, N = st.num_transitions_per_env, st.num_envs
-        B = T * N
         nmb = ppo.num_mini_batches
-        M = B // nmb
-        self._alloc(M)
-        self._mirrors_valid = False      # parameters may have changed since the last update
-        stream = C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
-        if ppo.desired_kl is not None and ppo.schedule == "adaptive":
-            self.optimizer.lr_dev.fill_(ppo.learning_rate)
-        # (fixed schedule: lr_dev keeps the optimizer's lr, i.e. a checkpoint's after load_state_dict,
-        # as torch.optim.Adam's param_groups do)
-        self.stats.zero_()
-        # as rsl_rl's generator; drawn on a second stream (the generator's offset is taken at issue,
-        # so the permutation is the same on any stream): its sort chain of small launches runs next
-        # to the rollout's last steps / GAE still queued on this stream instead of after them
+        M = ppo.storage.num_transitions_per_env * ppo.storage.num_envs // nmb
+        stream = self._begin_update(M)
+        # rsl_rl's permutation, drawn on a second stream (the generator's offset is taken at issue:
+        # the same permutation on any stream): its sort chain of small launches runs next to the
+        # rollout's last steps / GAE still queued on this stream instead of after them
         main = torch.cuda.current_stream(self.dev)
-        if getattr(self, "_perm_stream", None) is None:
+        if self._perm_stream is None:
             self._perm_stream = torch.cuda.Stream(self.dev)
         with torch.cuda.stream(self._perm_stream):
             indices = torch.randperm(nmb * M, requires_grad=False, device=self.dev)
         main.wait_stream(self._perm_stream)
         indices.record_stream(main)
-        obs = st.observations.view(B, -1)
-        cobs = st.privileged_observations.view(B, -1) if st.privileged_observations is not None else None
-        storage = dict(actions=st.actions.view(B, -1), old_logp=st.actions_log_prob.view(B),
-                       old_mu=st.mu.view(B, -1), old_sigma=st.sigma.view(B, -1), advantages=st.advantages.view(B),
-                       target_values=st.values.view(B), returns=st.returns.view(B))
+        obs, cobs, storage = self._storage_views()
         args = self._loss_args(storage)
-        xs = None
-        if self.lgx_gemm:
-            # rsl_rl draws ONE permutation per update and every epoch walks the same minibatches,
-            # so the padded layer-1 inputs are gathered once (one launch over all B rows) and a
-            # minibatch reads its contiguous slice: no per-minibatch gather
-            xs = self._gather_all(indices, obs, cobs, nmb * M, stream)
+        # rsl_rl draws ONE permutation per update and every epoch walks the same minibatches, so
+        # the padded layer-1 inputs are gathered once (one launch over all rows) and a minibatch
+        # reads its contiguous slice: no per-minibatch gather
+        xs = self._gather_all(indices, obs, cobs, nmb * M, stream) if self.lgx_gemm else [None] * nmb
         for _ in range(ppo.num_learning_epochs):
             for i in range(nmb):
-                idx = indices[i * M:(i + 1) * M]
-                if xs is None:
-                    mx = None
-                elif self.dw1_batched:        # [2, M, Kp] block: the same rows for actor and critic
-                    mx = (xs[0][i], None, xs[0][i])
-                else:
-                    mx = tuple(x[i * M:(i + 1) * M] if x is not None else None for x in xs)
-                self._minibatch(idx, obs, cobs, args, stream, xs=mx)
+                self._minibatch(indices[i * M:(i + 1) * M], obs, cobs, args, stream, xs=xs[i])
         self.host_issue_s = time.perf_counter() - t_issue   # host time to issue every launch (tools/host_overhead.py)
         return self._finish(ppo.num_learning_epochs * nmb, defer)
+
+    def _begin_update(self, M, reset=True):
+        """What every update() / gradients() call starts with: the plan for minibatches of M rows,
+        the run switches (held for all of the call's minibatches), and - reset - the learning rate
+        and statistics of a new update.  Returns the current stream's handle."""
+        self._alloc(M)
+        sw, ppo = _switches(), self.ppo
+        device_events = sw.dev_events and ppo.dist is None
+        self.run = SimpleNamespace(side_on=self.tn and sw.dw_side, early_reduce=sw.early_reduce,
+                                   device_events=device_events, bind=device_events and sw.bind,
+                                   dw1_batched=sw.dw1_batched)
+        self._mirrors_valid = False      # parameters may have changed since the last update
+        if reset:
+            # (fixed schedule: lr_dev keeps the optimizer's lr, i.e. a checkpoint's after
+            # load_state_dict, as torch.optim.Adam's param_groups do)
+            if ppo.desired_kl is not None and ppo.schedule == "adaptive":
+                self.optimizer.lr_dev.fill_(ppo.learning_rate)
+            self.stats.zero_()
+        return C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
+
+    def _storage_views(self):
+        """(obs, privileged obs or None, the loss kernel's seven storage arrays), flat over the
+        T x N transitions."""
+        st = self.ppo.storage
+        B = st.num_transitions_per_env * st.num_envs
+        obs = st.observations.view(B, -1)
+        cobs = st.privileged_observations.view(B, -1) if st.privileged_observations is not None else None
+        return obs, cobs, dict(actions=st.actions.view(B, -1), old_logp=st.actions_log_prob.view(B),
+                               old_mu=st.mu.view(B, -1), old_sigma=st.sigma.view(B, -1),
+                               advantages=st.advantages.view(B), target_values=st.values.view(B),
+                               returns=st.returns.view(B))
 
     def _finish(self, n, defer):
         """The update's readback (statistics, adapted learning rate) over its n minibatches: now, or
         deferred to pinned memory behind an event (resolve())."""
         if not defer:
             return self._apply_readback(self.stats.tolist(), float(self.optimizer.lr_dev.item()), n)
-        if getattr(self, "_pin_stats", None) is None:
+        if self._pin_stats is None:
             self._pin_stats = torch.empty(self.stats.shape, dtype=self.stats.dtype).pin_memory()
             self._pin_lr = torch.empty(1, dtype=self.optimizer.lr_dev.dtype).pin_memory()
             self._pin_ev = torch.cuda.Event()
@@ -652,12 +703,11 @@ class FusedPPOUpdate:
         self._pending = n
         return None
 
-
     # ------------------------------------------------------------------ recurrent policies
     def _rec_rows(self, i, T, N, envs):
         """Storage rows of recurrent minibatch i in the heads' row order (t-major over the envs
         [i envs, (i + 1) envs): the unpadded memory output [T, envs, H] flattened)."""
-        cache = getattr(self, "_rec_idx", None)
+        cache = self._rec_idx
         if cache is None or cache[0] != (T, N, envs):
             cache = ((T, N, envs), {})
             self._rec_idx = cache
@@ -677,20 +727,11 @@ class FusedPPOUpdate:
         ppo, ac = self.ppo, self.ppo.actor_critic
         st = ppo.storage
         T, N = st.num_transitions_per_env, st.num_envs
-        B = T * N
         nmb = ppo.num_mini_batches
         envs = N // nmb
         M = T * envs
-        self._alloc(M)
-        self._mirrors_valid = False
-        stream = C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
-        if ppo.desired_kl is not None and ppo.schedule == "adaptive":
-            self.optimizer.lr_dev.fill_(ppo.learning_rate)
-        self.stats.zero_()
-        storage = dict(actions=st.actions.view(B, -1), old_logp=st.actions_log_prob.view(B),
-                       old_mu=st.mu.view(B, -1), old_sigma=st.sigma.view(B, -1), advantages=st.advantages.view(B),
-                       target_values=st.values.view(B), returns=st.returns.view(B))
-        args = self._loss_args(storage)
+        stream = self._begin_update(M)
+        args = self._loss_args(self._storage_views()[2])
         H = self.num_obs
         k = 0
         for (obs_b, cobs_b, _a, _v, _adv, _r, _lp, _mu, _sg, hid_b, masks_b) in \
@@ -720,10 +761,9 @@ class FusedPPOUpdate:
         input gradient; dZ_1 from the fused backward), then torch autograd through the LSTM / GRU
         forward of this minibatch, written into the memories' blocks of the flat gradient (every
         other block is complete: this runs after the reductions, on the update's stream)."""
-        ctx = getattr(self, "_mem_ctx", None)
-        if ctx is None:
+        if self._mem_ctx is None:
             return
-        xa, xc = ctx
+        xa, xc = self._mem_ctx
         dz1 = self.D[0] if self.L > 1 else self.Y[self.L - 1]        # [2, M, h1]
         wa, wc = self.W[0]                                           # [h1, H] each
         dxa = torch.mm(dz1[0], wa).view_as(xa)
@@ -754,18 +794,19 @@ class FusedPPOUpdate:
         return self._apply_readback(self._pin_stats.tolist(), float(self._pin_lr[0]), n)
 
     def _gather_all(self, indices, obs, cobs, rows, stream):
-        # one input for both networks: rows gathered twice per minibatch ([nmb, 2, M, Kp]) so the
-        # layer-1 weight gradients of actor and critic are ONE batched split-K GEMM
-        self.dw1_batched = (cobs is None and self.num_obs == self.num_cobs and self.Xcp is None and 0 not in self.gemm_dw
-                            and os.environ.get("LGX_PPO_DW1_BATCHED", "1") != "0")
-        if self.dw1_batched:
-            M = self.M
-            if getattr(self, "Xall2", None) is None or self.Xall2.shape[0] * M != rows:
+        """The padded layer-1 input rows of the whole update in minibatch order: per minibatch the
+        `xs` of _minibatch_body."""
+        M = self.M
+        # one input for both networks and dW1 on the library bmm: rows gathered twice per minibatch
+        # ([nmb, 2, M, Kp]), so the layer-1 weight gradients of actor and critic are ONE batched GEMM
+        if (cobs is None and self.num_obs == self.num_cobs and self.Xcp is None and 0 not in self.gemm_dw
+                and self.run.dw1_batched):
+            if self.Xall2 is None or self.Xall2.shape[0] * M != rows:
                 self.Xall2 = torch.zeros(rows // M, 2, M, self.Kp, device=self.dev)
             self.check(self.lib.lgx_ppo_gather_rows_padded_dup(_vp(obs), _vp(self.Xall2), _vp(indices), rows,
                                                                obs.shape[1], self.Kp, M, stream), "gather")
-            return self.Xall2, None
-        if getattr(self, "Xall", None) is None or self.Xall.shape[0] != rows:
+            return [(x, None, x) for x in self.Xall2]
+        if self.Xall is None or self.Xall.shape[0] != rows:
             self.Xall = torch.zeros(rows, self.Kp, device=self.dev)     # padding columns stay zero
             self.Xcall = torch.zeros(rows, self.Kcp, device=self.dev) if self.Xcp is not None else None
         self.check(self.lib.lgx_ppo_gather_rows_padded(_vp(obs), _vp(self.Xall), _vp(indices), rows, obs.shape[1],
@@ -773,7 +814,7 @@ class FusedPPOUpdate:
         if cobs is not None:
             self.check(self.lib.lgx_ppo_gather_rows_padded(_vp(cobs), _vp(self.Xcall), _vp(indices), rows,
                                                            cobs.shape[1], self.Kcp, stream), "gather")
-        return self.Xall, self.Xcall
+        return [tuple(x[i:i + M] if x is not None else None for x in (self.Xall, self.Xcall)) for i in range(0, rows, M)]
 
     def _loss_args(self, storage):
         a = abi.LgxPpoLossArgs()
@@ -812,17 +853,8 @@ class FusedPPOUpdate:
         """Flat gradient of one minibatch (rows `idx` of the current storage), for tests."""
         if self.recurrent:   # (a recurrent minibatch is whole envs through the memories: update())
             raise NotImplementedError("gradients(idx) takes feed-forward policies; recurrent ones go through update()")
-        st = self.ppo.storage
-        T, N = st.num_transitions_per_env, st.num_envs
-        B = T * N
-        self._alloc(idx.numel())
-        self._mirrors_valid = False
-        stream = C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
-        obs = st.observations.view(B, -1)
-        cobs = st.privileged_observations.view(B, -1) if st.privileged_observations is not None else None
-        storage = dict(actions=st.actions.view(B, -1), old_logp=st.actions_log_prob.view(B),
-                       old_mu=st.mu.view(B, -1), old_sigma=st.sigma.view(B, -1), advantages=st.advantages.view(B),
-                       target_values=st.values.view(B), returns=st.returns.view(B))
+        stream = self._begin_update(idx.numel(), reset=False)
+        obs, cobs, storage = self._storage_views()
         self._minibatch(idx, obs, cobs, self._loss_args(storage), stream, apply=apply)
         return self.flat_g.clone()
 
@@ -835,20 +867,26 @@ class FusedPPOUpdate:
         self._t_period, self._t_count, self._t_events, self._t_mb = int(period), 0, [], 0
         self._c_events = []
 
+    def _bracket(self, torch_stream=None):
+        """In a timed minibatch (time_gemms): a pair of timing events, the first recorded on
+        `torch_stream` (None: the current stream); the caller records the second.  Else None."""
+        if not (self._t_period and self._t_count % self._t_period == 0):
+            return None
+        ev = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ev[0].record(torch_stream)
+        return ev
+
     def _all_reduce(self, buf, torch_stream):
         """ppo.dist.all_reduce(buf) issued on `torch_stream` (the current stream), with HIP events
         around it on that stream when this minibatch is timed."""
-        rec = getattr(self, "_t_period", 0) and self._t_count % self._t_period == 0
-        if rec:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(torch_stream)
+        ev = self._bracket(torch_stream)
         comm = self._lgx_comm()
         if comm is not None:   # lgx_allreduce_grads: RCCL on this stream itself (sum; 1/world in Adam)
             assert buf.dtype == torch.float32 and buf.is_contiguous()
             # one communicator, collectives issued from two streams (the bucketed update: side, then
             # main): RCCL orders nothing across streams, so a collective issued from another stream
             # than the previous one waits for it (torch's process group serialises on its own stream)
-            prev = getattr(self, "_comm_last", None)
+            prev = self._comm_last
             if prev is not None and prev[0] != torch_stream.cuda_stream:
                 torch_stream.wait_event(prev[1])
             self.check(self.lib.lgx_allreduce_grads(comm, _vp(buf), buf.numel(), 0,
@@ -858,25 +896,25 @@ class FusedPPOUpdate:
             self._comm_last = (torch_stream.cuda_stream, done)
         else:
             self.ppo.dist.all_reduce(buf)
-        if rec:
-            e1.record(torch_stream)
-            self._c_events.append((buf.numel() * buf.element_size(), e0, e1))
+        if ev:
+            ev[1].record(torch_stream)
+            self._c_events.append((buf.numel() * buf.element_size(), *ev))
 
     @property
     def allreduce_impl(self):
         """"lgx" (lgx_allreduce_grads on the library's own RCCL communicator, LGX_NATIVE_ALLREDUCE=1
         with the nccl backend) or "torch" (torch.distributed.all_reduce, the default)."""
-        return "lgx" if getattr(self, "_comm", None) is not None else "torch"
+        return "lgx" if self._comm not in (None, _UNTRIED) else "torch"
 
     def _lgx_comm(self):
         """The rank's lgx_comm, created collectively at the first gradient all-reduce when
         LGX_NATIVE_ALLREDUCE=1 and the process group is nccl (RCCL): rank 0 draws the unique id,
         the group broadcasts it; the RCCL library is torch's own (one RCCL instance per process)."""
-        if hasattr(self, "_comm"):
+        if self._comm is not _UNTRIED:
             return self._comm
-        self._comm = None
+        self._comm = None   # (tried: the torch path unless a communicator is created below)
         dist = self.ppo.dist
-        if os.environ.get("LGX_NATIVE_ALLREDUCE", "0") != "1":
+        if not _switches().native_allreduce:
             return None
         # asked for: fail loudly rather than fall back to torch.distributed (the 8-GPU run must use
         # the path it was configured for) or load an RCCL other than the one torch's nccl backend runs
@@ -902,8 +940,8 @@ class FusedPPOUpdate:
 
     def close_comm(self):
         """Destroy the lgx_comm (collective: every rank calls it after its last update)."""
-        comm, self._comm = getattr(self, "_comm", None), None
-        if comm is not None:
+        comm, self._comm = self._comm, None
+        if comm not in (None, _UNTRIED):
             torch.cuda.synchronize(self.dev)
             self.check(self.lib.lgx_comm_destroy(comm), "comm_destroy")
 
@@ -911,29 +949,34 @@ class FusedPPOUpdate:
         """(collectives timed, total ms, total bytes, timed minibatches) of the all-reduces of the
         timed minibatches."""
         torch.cuda.synchronize()
-        ev = getattr(self, "_c_events", [])
-        return (len(ev), sum(e0.elapsed_time(e1) for _, e0, e1 in ev), sum(b for b, _, _ in ev),
-                getattr(self, "_t_mb", 0))
+        ev = self._c_events
+        return len(ev), sum(e0.elapsed_time(e1) for _, e0, e1 in ev), sum(b for b, _, _ in ev), self._t_mb
 
     def _gemm(self, g, stream):
-        rec = getattr(self, "_t_period", 0) and self._t_count % self._t_period == 0
-        if rec:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
+        ev = self._bracket()
         self.check(self.lib.lgx_gemm_nt(C.byref(g), stream), "gemm_nt")
-        if rec:
-            e1.record()
+        if ev:
+            ev[1].record()
             # algorithmic FLOP: the unpadded K of layer 1 (num_obs), not the zero-padded columns
             k = self.k_alg.get(id(g), g.K)
-            self._t_events.append((g.epi, 2.0 * g.M * g.N * k * g.batch, e0, e1))
+            self._t_events.append((g.epi, 2.0 * g.M * g.N * k * g.batch, *ev))
 
     @property
     def join_events(self):
-        """"device" (lgx_event_*) or "system" (torch events): the event kind _join uses."""
-        return "device" if (os.environ.get("LGX_PPO_DEV_EVENTS", "1") != "0" and self.ppo.dist is None) else "system"
+        """"device" (lgx_event_*) or "system" (torch events): the event kind an update started now
+        would join its streams with (an update in progress keeps what it started with)."""
+        return "device" if _switches().dev_events and self.ppo.dist is None else "system"
+
+    def _side_stream(self):
+        """The backward's second stream (with the torch events of its joins), created on first use."""
+        if self._side is None:
+            self._side = torch.cuda.Stream(self.dev)
+            self._ev_in = [torch.cuda.Event() for _ in range(self.L)]
+            self._ev_out = torch.cuda.Event()
+        return self._side
 
     def _device_events(self):
-        if getattr(self, "_dev_ev", None) is None:
+        if self._dev_ev is None:
             self._dev_ev = []
             for _ in range(self.L + 1):
                 e = C.c_void_p()
@@ -943,9 +986,9 @@ class FusedPPOUpdate:
 
     def _arm(self, slot):
         """Bind join `slot`'s device event to the next lgx launch (the producer's last one), so the
-        join records no separate event packet on the producer stream: each record left the stream
-        idle ~5 us between two kernels.  LGX_PPO_BIND=0: recorded at the join as before."""
-        if self.join_events != "device" or os.environ.get("LGX_PPO_BIND", "1") == "0":
+        join records no separate event packet on the producer stream.  LGX_PPO_BIND=0, or torch
+        events: recorded at the join."""
+        if not self.run.bind:
             return
         self.check(self.lib.lgx_launch_bind_event(self._device_events()[slot]), "launch_bind_event")
         self._armed = slot
@@ -953,12 +996,12 @@ class FusedPPOUpdate:
     def _join(self, src, dst, slot):
         """Order `dst` after the work issued so far on `src` (slot: 0..L-1 the side stream's inputs,
         L its output).  Device-scope events (lgx_event_*: no system-scope cache write-back and
-        invalidate at the record) in single-process runs unless LGX_PPO_DEV_EVENTS=0 (torch events;
-        read per call for same-process A/B runs).  Data-parallel runs keep the system-scope events:
-        the joins there also order the collectives' buffers, which peers write over xGMI."""
-        if self.join_events == "device":
+        invalidate at the record) in single-process runs unless LGX_PPO_DEV_EVENTS=0 (torch
+        events).  Data-parallel runs keep the system-scope events: the joins there also order the
+        collectives' buffers, which peers write over xGMI."""
+        if self.run.device_events:
             e = self._device_events()[slot]
-            armed, self._armed = getattr(self, "_armed", None), None
+            armed, self._armed = self._armed, None
             # bound to the producer's last launch by _arm (no record packet on `src`), else recorded
             if armed != slot or self.lib.lgx_launch_bind_pending():
                 if armed is not None:
@@ -971,32 +1014,30 @@ class FusedPPOUpdate:
             dst.wait_event(e)
 
     def __del__(self):
-        for e in getattr(self, "_dev_ev", None) or []:
+        for e in self._dev_ev or []:
             try:
                 self.lib.lgx_event_destroy(e)
             except Exception:
                 pass
 
     def _gemm_tn(self, t, stream, torch_stream=None):
-        rec = getattr(self, "_t_period", 0) and self._t_count % self._t_period == 0   # (as _gemm)
-        if rec:   # (events on the stream the kernel runs on)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(torch_stream)
+        ev = self._bracket(torch_stream)   # (events on the stream the kernel runs on)
         self.check(self.lib.lgx_gemm_tn(C.byref(t), stream), "gemm_tn")
-        if rec:
-            e1.record(torch_stream)
-            self._t_events.append(("tn", 2.0 * t.M * t.R * t.Cc * t.batch, e0, e1))
+        if ev:
+            ev[1].record(torch_stream)
+            self._t_events.append(("tn", 2.0 * t.M * t.R * t.Cc * t.batch, *ev))
 
     def gemm_timings(self):
         """{epilogue: (launches, total ms, total algorithmic FLOP, timed minibatches)} of the timed
         launches."""
         torch.cuda.synchronize()
         out = {}
-        for epi, flop, e0, e1 in getattr(self, "_t_events", []):
+        for epi, flop, e0, e1 in self._t_events:
             n, ms, f, _ = out.get(epi, (0, 0.0, 0.0, 0))
             out[epi] = (n + 1, ms + e0.elapsed_time(e1), f + flop, self._t_mb)
         return out
 
+    # ------------------------------------------------------------------ one minibatch
     @torch.no_grad()
     def _minibatch(self, idx, obs, cobs, args, stream, apply=True, xs=None):
         with self.tuned:     # TunableOp table on for the library GEMMs of this minibatch only
@@ -1004,211 +1045,254 @@ class FusedPPOUpdate:
 
     def _minibatch_body(self, idx, obs, cobs, args, stream, apply=True, xs=None):
         """One minibatch: rows `idx` of the storage; `xs` = their padded layer-1 inputs already
-        gathered (slices of _gather_all's buffers), None = gather here."""
-        lib, chk = self.lib, self.check
+        gathered (slices of _gather_all's buffers), None = gather here.  `stream` is the current
+        stream's handle; the run switches are those of the enclosing update() / gradients() call."""
         ppo = self.ppo
-        M, S, h, L, A = self.M, self.S, self.hidden, self.L, self.A
-        if getattr(self, "_t_period", 0):
+        if self._t_period:
             self._t_mb += self._t_count % self._t_period == 0
             self._t_count += 1
-        fused = self.lgx_gemm
-        X = Xc = self.X
-        if fused:
-            if not self._mirrors_valid:   # (afterwards lgx_adam_clip_mirror keeps the copies current)
-                if self.split:
-                    chk(lib.lgx_split_bf16(self.copy_jobs, len(self.copy_jobs), stream), "split_bf16")
-                else:
-                    chk(lib.lgx_copy2d(self.copy_jobs, len(self.copy_jobs), stream), "copy2d")
-                self._mirrors_valid = True
-            if xs is None:
-                chk(lib.lgx_ppo_gather_rows_padded(_vp(obs), _vp(self.Xp), _vp(idx), M, obs.shape[1], self.Kp,
-                                                   stream), "gather")
-                if cobs is not None:
-                    chk(lib.lgx_ppo_gather_rows_padded(_vp(cobs), _vp(self.Xcp), _vp(idx), M, cobs.shape[1],
-                                                       self.Kcp, stream), "gather")
-                xp, xcp = self.Xp, self.Xcp
-            else:
-                xp, xcp = xs[0], xs[1]
-                if len(xs) > 2:                 # [2, M, Kp]: net 0's copy feeds the forward
-                    xp = xs[0][0]
-            X = Xc = xp[:, :self.num_obs]
-            if cobs is not None or self.recurrent:
-                Xc = xcp[:, :self.num_cobs]
-            for g, src in zip(self.gemm_fwd[0], self.fwd0_src):
-                g.A = (xp if src == "x" or xcp is None else xcp).data_ptr()
+        if self.lgx_gemm:
+            inp = self._inputs_lgx(idx, obs, cobs, stream, xs)
+            self._forward_lgx(stream)
         else:
-            chk(lib.lgx_ppo_gather_rows(_vp(obs), _vp(self.X), _vp(idx), M, obs.shape[1], stream), "gather")
+            inp = self._inputs_lib(idx, obs, cobs, stream)
+            self._forward_lib(inp, stream)
+        self._loss_and_heads(idx, args, stream)
+        dZ, side_used = self._backward_lgx(stream) if self.lgx_gemm else self._backward_lib(stream)
+        # every gradient block but dW1's is complete once dA_1 (this stream) and the side stream's
+        # dW GEMMs are: they are reduced early, on the side stream, while dW1 runs here
+        early = side_used and self.loss_bwd and len(self.jobs_rest) > 0 and self.run.early_reduce
+        # the clip norm's sums of squares from the reduction launches (their buffer, or 0)
+        sq = self.sq_parts.data_ptr() if self.fused_sq and apply and ppo.dist is None else 0
+        self.bucketed = early and apply and ppo.dist is not None and not self.recurrent
+        if early:
+            self._reduce_rest_on_side(args, sq)
+        self._dw1(inp, dZ, stream)
+        nsq = self._reduce(args, sq, early, side_used, stream)
+        if self.recurrent:
+            self._memory_backward()
+        if apply:
+            grad_scale = self._all_reduce_gradient(stream) if ppo.dist is not None else 1.0
+            self._optimizer_step(sq, nsq, grad_scale, stream)
+
+    # ---- inputs: the layer-1 rows of both networks.  X / Xc are the unpadded rows (library
+    # GEMMs), xp / xcp the rows padded to the GEMM's K step (lgx GEMMs; xcp None: one input for
+    # both networks), dup the [2, M, Kp] block of _gather_all's duplicated rows (batched dW1)
+    def _inputs_lgx(self, idx, obs, cobs, stream, xs):
+        lib, chk, M = self.lib, self.check, self.M
+        if not self._mirrors_valid:   # (afterwards lgx_adam_clip_mirror keeps the weight copies current)
+            if self.split:
+                chk(lib.lgx_split_bf16(self.copy_jobs, len(self.copy_jobs), stream), "split_bf16")
+            else:
+                chk(lib.lgx_copy2d(self.copy_jobs, len(self.copy_jobs), stream), "copy2d")
+            self._mirrors_valid = True
+        dup = None
+        if xs is None:
+            chk(lib.lgx_ppo_gather_rows_padded(_vp(obs), _vp(self.Xp), _vp(idx), M, obs.shape[1], self.Kp,
+                                               stream), "gather")
             if cobs is not None:
-                chk(lib.lgx_ppo_gather_rows(_vp(cobs), _vp(self.Xc), _vp(idx), M, cobs.shape[1], stream), "gather")
-                Xc = self.Xc
-        # ---- forward
-        wa, wc = self.W[0]
-        fp = self.flat_p
-        if fused:
-            for g in self.gemm_fwd[0]:
-                self._gemm(g, stream)
-            for k in range(1, L):
-                if k in self.lgx_fwd_layers:
-                    self._gemm(self.gemm_fwd[k], stream)
-                else:
-                    torch.bmm(self.Y[k - 1], self.W[k].transpose(1, 2), out=self.Y[k])
-                    chk(lib.lgx_bias_act(_vp(self.Y[k]), C.c_void_p(fp.data_ptr() + 4 * self.bo[k]), M, h[k], 2, 1,
-                                         stream), "bias")
+                chk(lib.lgx_ppo_gather_rows_padded(_vp(cobs), _vp(self.Xcp), _vp(idx), M, cobs.shape[1],
+                                                   self.Kcp, stream), "gather")
+            xp, xcp = self.Xp, self.Xcp
+        elif len(xs) > 2:                   # [2, M, Kp]: net 0's copy feeds the forward
+            xp, xcp, dup = xs[0][0], xs[1], xs[2]
         else:
-            if cobs is None:   # shared input: one batched GEMM over {actor, critic} with a stride-0 input
-                torch.bmm(X.unsqueeze(0).expand(2, M, self.num_obs), self.W1s.transpose(1, 2), out=self.Y[0])
-            else:
-                torch.mm(X, wa.t(), out=self.Y[0][0])
-                torch.mm(Xc, wc.t(), out=self.Y[0][1])
-            chk(lib.lgx_bias_act(_vp(self.Y[0]), C.c_void_p(fp.data_ptr() + 4 * self.bo[0]), M, h[0], 2, 1, stream),
-                "bias")
-            for k in range(1, L):
-                torch.bmm(self.Y[k - 1], self.W[k].transpose(1, 2), out=self.Y[k])
-                chk(lib.lgx_bias_act(_vp(self.Y[k]), C.c_void_p(fp.data_ptr() + 4 * self.bo[k]), M, h[k], 2, 1,
-                                     stream), "bias")
+            xp, xcp = xs
+        X = Xc = xp[:, :self.num_obs]
+        if cobs is not None or self.recurrent:
+            Xc = xcp[:, :self.num_cobs]
+        for g, x in zip(self.gemm_fwd[0], (xp, xcp if xcp is not None else xp)):   # (one launch, or one per network)
+            g.A = x.data_ptr()
+        return SimpleNamespace(X=X, Xc=Xc, xp=xp, xcp=xcp, dup=dup)
+
+    def _inputs_lib(self, idx, obs, cobs, stream):
+        lib, chk, M = self.lib, self.check, self.M
+        X = Xc = self.X
+        chk(lib.lgx_ppo_gather_rows(_vp(obs), _vp(X), _vp(idx), M, obs.shape[1], stream), "gather")
+        if cobs is not None:
+            Xc = self.Xc
+            chk(lib.lgx_ppo_gather_rows(_vp(cobs), _vp(Xc), _vp(idx), M, cobs.shape[1], stream), "gather")
+        return SimpleNamespace(X=X, Xc=Xc, xp=None, xcp=None, dup=None)
+
+    # ---- forward: the hidden layers into Y[k] ([2, M, h_k], actor and critic batched)
+    def _forward_lgx(self, stream):
+        for g in self.gemm_fwd[0]:
+            self._gemm(g, stream)
+        for k in range(1, self.L):
+            if k in self.lgx_fwd_layers:
+                self._gemm(self.gemm_fwd[k], stream)
+            else:                           # (LGX_PPO_GEMM=auto)
+                self._bmm_bias_elu(k, stream)
+
+    def _forward_lib(self, inp, stream):
+        if inp.Xc is inp.X:   # shared input: one batched GEMM over {actor, critic} with a stride-0 input
+            torch.bmm(inp.X.unsqueeze(0).expand(2, self.M, self.num_obs), self.W1s.transpose(1, 2), out=self.Y[0])
+        else:
+            wa, wc = self.W[0]
+            torch.mm(inp.X, wa.t(), out=self.Y[0][0])
+            torch.mm(inp.Xc, wc.t(), out=self.Y[0][1])
+        self._bias_elu(0, stream)
+        for k in range(1, self.L):
+            self._bmm_bias_elu(k, stream)
+
+    def _bmm_bias_elu(self, k, stream):
+        """Hidden layer k >= 1 on the library GEMM + lgx_bias_act."""
+        torch.bmm(self.Y[k - 1], self.W[k].transpose(1, 2), out=self.Y[k])
+        self._bias_elu(k, stream)
+
+    def _bias_elu(self, k, stream):
+        self.check(self.lib.lgx_bias_act(_vp(self.Y[k]), C.c_void_p(self.flat_p.data_ptr() + 4 * self.bo[k]), self.M,
+                                         self.hidden[k], 2, 1, stream), "bias")
+
+    # ---- loss, gradient at the heads (dZ of the last hidden layer, in place over Y[L-1]), KL ->
+    # adaptive learning rate (single process: in the loss finalize)
+    def _loss_and_heads(self, idx, args, stream):
+        lib, chk, L = self.lib, self.check, self.L
         wha, whc = self.W[L]
         if not self.head_in_loss:
             torch.mm(self.Y[L - 1][0], wha.t(), out=self.MU)
             torch.mm(self.Y[L - 1][1], whc.t(), out=self.V)
-        # ---- loss, gradient at the heads, KL -> adaptive learning rate
         args.idx = idx.data_ptr()
-        adaptive = ppo.desired_kl is not None and ppo.schedule == "adaptive"   # (single process: in the loss finalize)
-        side_on = self.tn and os.environ.get("LGX_PPO_DW_SIDE", "1") != "0"
         if self.loss_bwd:
-            # loss + output-layer backward in one launch (dZ3 over Y[L-1]); finalize in the reduction
-            if side_on and (L - 1) in self.gemm_dw:
+            # loss + output-layer backward in one launch; its finalize runs in the reduction
+            if self.run.side_on and (L - 1) in self.gemm_dw:
                 self._arm(L - 1)   # (the first join's producer)
             chk(lib.lgx_ppo_loss_bwd(C.byref(args), _vp(self.head_parts), stream), "lgx_ppo_loss_bwd")
         else:
             chk(lib.lgx_ppo_loss(C.byref(args), stream), "lgx_ppo_loss")
-            # ---- backward (+ the loss finalize on one extra workgroup of the same launch)
+            # output-layer backward (+ the loss finalize on one extra workgroup of the same launch)
             chk(lib.lgx_head_bwd_finalize(C.byref(args), _vp(self.dMU), _vp(self.dV), _vp(wha), _vp(whc),
-                                          _vp(self.Y[L - 1]), M, A, h[-1], _vp(self.head_parts), stream), "head_bwd")
-        dZ = self.Y[L - 1]                           # dZ of the last hidden layer (in place)
-        # dW_k (lgx_gemm_tn) of the hidden layers on a second stream, concurrent with dA_k on this
-        # one (both only read dZ_k and Y_{k-1}): the weight-gradient tiles fill the CUs that the
-        # dA launch's last round leaves idle (measured 19.3 -> 19.0 ms per iteration);
-        # LGX_PPO_DW_SIDE=0 keeps every launch on one stream
-        side_used = False
+                                          _vp(self.Y[L - 1]), self.M, self.A, self.hidden[-1], _vp(self.head_parts),
+                                          stream), "head_bwd")
+
+    # ---- backward through the hidden layers L-1 .. 1: dW_k = dZ_k^T Y_{k-1} split-K over Sk[k] row
+    # slices into P[k] (reduced later), dZ_{k-1} = (dZ_k W_k) * elu'(Y_{k-1}), dZ_{L-1} in Y[L-1].
+    # Both return (dZ_1, whether the side stream was used)
+    def _backward_lgx(self, stream):
+        """dW_k (lgx_gemm_tn) on a second stream, each right after its own join, concurrent with
+        dA_k on this one (both only read dZ_k and Y_{k-1}); LGX_PPO_DW_SIDE=0 keeps every launch
+        on one stream; a dW that is not on lgx_gemm_tn takes the library bmm on this one."""
+        L, dw = self.L, self.gemm_dw
+        side = main = None
+        if self.run.side_on and any(k in dw for k in range(1, L)):
+            side, main = self._side_stream(), torch.cuda.current_stream(self.dev)
+        dw_stream = C.c_void_p(side.cuda_stream) if side is not None else stream
         for k in range(L - 1, 0, -1):
-            # dW_k = dZ_k^T Y_{k-1}, split-K over S row slices (partials reduced below); each dW on
-            # the side stream right after its own join (dW3 held back to dA3's join, so that it
-            # shares one join with dW2: 10.47 -> 10.82 ms per update - the dA3 / dW3 overlap is worth
-            # more than the join)
-            Sl = self.Sk[k]
-            if k in self.gemm_dw and side_on:
-                if getattr(self, "_side", None) is None:
-                    self._side = torch.cuda.Stream(self.dev)
-                    self._ev_in = [torch.cuda.Event() for _ in range(L)]
-                    self._ev_out = torch.cuda.Event()
-                main = torch.cuda.current_stream(self.dev)
-                self._join(main, self._side, k)
-                for t in self.gemm_dw[k]:
-                    self._gemm_tn(t, C.c_void_p(self._side.cuda_stream), self._side)
-                side_used = True
-            elif k in self.gemm_dw:
-                for t in self.gemm_dw[k]:
-                    self._gemm_tn(t, stream)
+            if k not in dw:
+                self._dw_bmm(k)
             else:
-                torch.bmm(dZ.view(2 * Sl, M // Sl, h[k]).transpose(1, 2),
-                          self.Y[k - 1].view(2 * Sl, M // Sl, h[k - 1]), out=self.P[k])
-            if fused:
-                if side_on and k - 1 >= 1 and (k - 1) in self.gemm_dw:
-                    self._arm(k - 1)   # (the next join's producer: this dA launch)
-                self._gemm(self.gemm_bwd[k], stream)
-            else:
-                torch.bmm(dZ, self.W[k], out=self.D[k - 1])
-                chk(lib.lgx_elu_bwd_colsum(_vp(self.D[k - 1]), _vp(self.Y[k - 1]), M, h[k - 1], 2,
-                                           _vp(self.col_parts[k - 1]), stream), "elu_bwd")
-            dZ = self.D[k - 1]
-        early = (side_used and self.loss_bwd and len(self.jobs_rest) > 0
-                 and os.environ.get("LGX_PPO_EARLY_REDUCE", "1") != "0")
-        use_sq = self.fused_sq and apply and ppo.dist is None
-        step_p = _vp(self.optimizer.step_dev) if use_sq else None
-        sq = self.sq_parts.data_ptr() if use_sq else 0
-        nsq = 0
-        if early:
-            # every gradient block but dW1's is complete once dA_1 (this stream) and the side
-            # stream's dW GEMMs are: reduce them (+ the loss finalize) on the side stream while dW1
-            # runs here - the memory-bound reduction next to the MFMA-bound GEMM
-            if not self.rest_on_side:   # (skipping the join when possible: 10.478 -> 10.468 ms per update)
-                self._join(torch.cuda.current_stream(self.dev), self._side, 0)
-            self._arm(L)   # (the final join's producer: the side stream's last launch)
-            if use_sq:
-                chk(lib.lgx_reduce_slices_sq(self.jobs_rest, len(self.jobs_rest), C.byref(args), C.c_void_p(sq), step_p,
-                                             C.c_void_p(self._side.cuda_stream)), "reduce")
-            else:
-                chk(lib.lgx_reduce_slices_finalize(self.jobs_rest, len(self.jobs_rest), C.byref(args),
-                                                   C.c_void_p(self._side.cuda_stream)), "reduce")
-        bucketed = early and apply and ppo.dist is not None and not self.recurrent
-        self.bucketed = bucketed
-        if bucketed:
-            # data-parallel: the first gradient bucket (every block after dW1's in the layer-major
-            # flat layout + the KL slot) is all-reduced from the side stream as soon as it is
-            # reduced, concurrent with dW1's GEMM here; dW1's bucket follows below (one
-            # communicator: the collectives run in issue order on every rank)
-            with torch.cuda.stream(self._side):
-                self.g_comm[self.n:].copy_(self.stats[0:1])
-                self._all_reduce(self.g_comm[self.nW1:], self._side)
-        if 0 in self.gemm_dw and fused:     # lgx_gemm_tn over the minibatch's padded input rows
-            t = self.gemm_dw[0]
-            t[0].B = xp.data_ptr()
-            if len(t) > 1:
-                t[1].B = (xcp if xcp is not None else xp).data_ptr()
-            for tk in t:
-                self._gemm_tn(tk, stream)
-        elif xs is not None and len(xs) > 2:    # one batched GEMM: 2 networks x S row slices
-            x2 = xs[2].view(2 * S, M // S, self.Kp)[:, :, :self.num_obs]
+                if side is not None:
+                    self._join(main, side, k)
+                for t in dw[k]:
+                    self._gemm_tn(t, dw_stream, side)
+            if side is not None and k - 1 >= 1 and (k - 1) in dw:
+                self._arm(k - 1)   # (the next join's producer: this dA launch)
+            self._gemm(self.gemm_bwd[k], stream)
+        return self._dz(0), side is not None
+
+    def _backward_lib(self, stream):
+        for k in range(self.L - 1, 0, -1):
+            self._dw_bmm(k)
+            torch.bmm(self._dz(k), self.W[k], out=self.D[k - 1])
+            self.check(self.lib.lgx_elu_bwd_colsum(_vp(self.D[k - 1]), _vp(self.Y[k - 1]), self.M, self.hidden[k - 1], 2,
+                                                   _vp(self.col_parts[k - 1]), stream), "elu_bwd")
+        return self._dz(0), False
+
+    def _dz(self, k):
+        return self.Y[k] if k == self.L - 1 else self.D[k]
+
+    def _dw_bmm(self, k):
+        """dW_k, k >= 1, on the library bmm over the row slices."""
+        M, Sl, h = self.M, self.Sk[k], self.hidden
+        torch.bmm(self._dz(k).view(2 * Sl, M // Sl, h[k]).transpose(1, 2),
+                  self.Y[k - 1].view(2 * Sl, M // Sl, h[k - 1]), out=self.P[k])
+
+    def _dw1(self, inp, dZ, stream):
+        """The layer-1 weight gradient, on the main stream."""
+        M, S, h = self.M, self.S, self.hidden
+        if 0 in self.gemm_dw:               # lgx_gemm_tn over the minibatch's padded input rows
+            for t, x in zip(self.gemm_dw[0], (inp.xp, inp.xcp if inp.xcp is not None else inp.xp)):
+                t.B = x.data_ptr()
+                self._gemm_tn(t, stream)
+        elif inp.dup is not None:           # one batched GEMM: 2 networks x S row slices
+            x2 = inp.dup.view(2 * S, M // S, self.Kp)[:, :, :self.num_obs]
             torch.bmm(dZ.view(2 * S, M // S, h[0]).transpose(1, 2), x2, out=self.P[0].view(2 * S, h[0], self.num_obs))
         else:
-            torch.bmm(dZ[0].view(S, M // S, h[0]).transpose(1, 2), X.unflatten(0, (S, M // S)), out=self.P[0][0])
-            torch.bmm(dZ[1].view(S, M // S, h[0]).transpose(1, 2), Xc.unflatten(0, (S, M // S)), out=self.P[0][1])
-        if side_used and not early:   # the weight gradients are complete before the reduction reads them
-            self._join(self._side, torch.cuda.current_stream(self.dev), L)
-        if early:   # (dW1's partials come from this stream; the side stream's blocks are joined below)
-            if use_sq:
-                chk(lib.lgx_reduce_slices_sq(self.jobs_dw1, len(self.jobs_dw1), None, C.c_void_p(sq + 4 * self.nsq_rest),
-                                             None, stream), "reduce")
-                nsq = self.nsq_rest + self.nsq_dw1
-            else:
-                chk(lib.lgx_reduce_slices(self.jobs_dw1, len(self.jobs_dw1), stream), "reduce")
-            if bucketed:
-                self._all_reduce(self.g_comm[:self.nW1], torch.cuda.current_stream(self.dev))
-            self._join(self._side, torch.cuda.current_stream(self.dev), L)
-        elif self.loss_bwd and use_sq:
-            chk(lib.lgx_reduce_slices_sq(self.jobs, self.njobs, C.byref(args), C.c_void_p(sq), step_p, stream), "reduce")
-            nsq = self.nsq_all
-        elif self.loss_bwd:
-            chk(lib.lgx_reduce_slices_finalize(self.jobs, self.njobs, C.byref(args), stream), "reduce")
+            torch.bmm(dZ[0].view(S, M // S, h[0]).transpose(1, 2), inp.X.unflatten(0, (S, M // S)), out=self.P[0][0])
+            torch.bmm(dZ[1].view(S, M // S, h[0]).transpose(1, 2), inp.Xc.unflatten(0, (S, M // S)), out=self.P[0][1])
+
+    # ---- reductions of the split-K / bias partials into the flat gradient; data-parallel buckets
+    def _reduce_launch(self, jobs, args, sq, stream):
+        """One reduction launch over `jobs`; args: with the loss finalize (loss_bwd); sq: writing the
+        clip norm's sum-of-squares partials there (the step counter advanced with the finalize)."""
+        lib, n = self.lib, len(jobs)
+        if sq:
+            rc = lib.lgx_reduce_slices_sq(jobs, n, C.byref(args) if args is not None else None, C.c_void_p(sq),
+                                          _vp(self.optimizer.step_dev) if args is not None else None, stream)
+        elif args is not None:
+            rc = lib.lgx_reduce_slices_finalize(jobs, n, C.byref(args), stream)
         else:
-            chk(lib.lgx_reduce_slices(self.jobs, self.njobs, stream), "reduce")
-        if self.recurrent:
-            self._memory_backward()
-        if not apply:
-            return
-        grad_scale = 1.0
-        if ppo.dist is not None:
-            # summed gradient + summed KL (rsl_rl adapts the LR before the step, only the optimizer
-            # step reads it, so adapting after the backward is equivalent): two buckets issued
-            # above, or one collective here
-            if not bucketed:
+            rc = lib.lgx_reduce_slices(jobs, n, stream)
+        self.check(rc, "reduce")
+
+    def _reduce_rest_on_side(self, args, sq):
+        """The early reduction: every job but dW1's (+ the loss finalize) on the side stream, the
+        memory-bound reduction next to the MFMA-bound dW1 GEMM on the main one.  Data-parallel:
+        that bucket (every block after dW1's in the flat layout + the KL slot) is all-reduced from
+        the side stream right away; dW1's follows in _reduce (one communicator: the collectives run
+        in issue order on every rank)."""
+        side = self._side
+        if not self.rest_on_side:   # (a rest job reads a dA epilogue's partials from the main stream)
+            self._join(torch.cuda.current_stream(self.dev), side, 0)
+        self._arm(self.L)   # (the final join's producer: the side stream's last launch)
+        self._reduce_launch(self.jobs_rest, args, sq, C.c_void_p(side.cuda_stream))
+        if self.bucketed:
+            with torch.cuda.stream(side):
                 self.g_comm[self.n:].copy_(self.stats[0:1])
-                self._all_reduce(self.g_comm, torch.cuda.current_stream(self.dev))
-            grad_scale = 1.0 / ppo.dist.get_world_size()
-            if adaptive:
-                chk(lib.lgx_ppo_adapt_lr(C.c_void_p(self.g_comm.data_ptr() + 4 * self.n), grad_scale,
-                                         _vp(self.optimizer.lr_dev), ppo.desired_kl, stream), "adapt_lr")
-        o = self.optimizer
-        if fused and nsq:   # (norm from the reductions' sums of squares; step advanced there)
-            chk(lib.lgx_adam_clip_mirror_sq(_vp(self.flat_p), _vp(self.flat_g), _vp(o.m), _vp(o.v), self.n, C.c_void_p(sq),
-                                            nsq, ppo.max_grad_norm, _vp(o.lr_dev), _vp(o.step_dev), o.betas[0],
-                                            o.betas[1], o.eps, self.copy_jobs, len(self.copy_jobs), stream), "adam")
-        elif fused:   # the step also refreshes the GEMM weight copies (padded W1, transposed W2..)
-            chk(lib.lgx_adam_clip_mirror(_vp(self.flat_p), _vp(self.flat_g), _vp(o.m), _vp(o.v), self.n,
-                                         _vp(self.norm_parts), self.norm_parts.numel(), grad_scale, ppo.max_grad_norm,
-                                         _vp(o.lr_dev), _vp(o.step_dev), o.betas[0], o.betas[1], o.eps, self.copy_jobs,
-                                         len(self.copy_jobs), stream), "adam")
+                self._all_reduce(self.g_comm[self.nW1:], side)
+
+    def _reduce(self, args, sq, early, side_used, stream):
+        """On the main stream after dW1: its jobs (early: the rest is on the side stream, joined
+        here) or all jobs in one launch.  Returns the number of sum-of-squares partials written."""
+        main = torch.cuda.current_stream(self.dev)
+        if not early:
+            if side_used:   # the weight gradients are complete before the reduction reads them
+                self._join(self._side, main, self.L)
+            sq = sq if self.loss_bwd else 0
+            self._reduce_launch(self.jobs, args if self.loss_bwd else None, sq, stream)
+            return self.nsq_all if sq else 0
+        self._reduce_launch(self.jobs_dw1, None, sq + 4 * self.nsq_rest if sq else 0, stream)
+        if self.bucketed:
+            self._all_reduce(self.g_comm[:self.nW1], main)
+        self._join(self._side, main, self.L)
+        return self.nsq_rest + self.nsq_dw1 if sq else 0
+
+    def _all_reduce_gradient(self, stream):
+        """Data-parallel: summed gradient + summed KL (rsl_rl adapts the LR before the step, only
+        the optimizer step reads it, so adapting after the backward is equivalent): the two buckets
+        issued by the reductions, or one collective here.  Returns the gradient's scale 1 / world."""
+        ppo = self.ppo
+        if not self.bucketed:
+            self.g_comm[self.n:].copy_(self.stats[0:1])
+            self._all_reduce(self.g_comm, torch.cuda.current_stream(self.dev))
+        grad_scale = 1.0 / ppo.dist.get_world_size()
+        if ppo.desired_kl is not None and ppo.schedule == "adaptive":
+            self.check(self.lib.lgx_ppo_adapt_lr(C.c_void_p(self.g_comm.data_ptr() + 4 * self.n), grad_scale,
+                                                 _vp(self.optimizer.lr_dev), ppo.desired_kl, stream), "adapt_lr")
+        return grad_scale
+
+    # ---- optimizer step: clip_grad_norm_ + Adam on the flat buffers
+    def _optimizer_step(self, sq, nsq, grad_scale, stream):
+        lib, o, clip = self.lib, self.optimizer, self.ppo.max_grad_norm
+        bufs = (_vp(self.flat_p), _vp(self.flat_g), _vp(o.m), _vp(o.v), self.n)
+        norm = (_vp(self.norm_parts), self.norm_parts.numel(), grad_scale, clip)   # (its own sum-of-squares pass)
+        adam = (_vp(o.lr_dev), _vp(o.step_dev), o.betas[0], o.betas[1], o.eps)
+        mirrors = (self.copy_jobs, len(self.copy_jobs)) if self.lgx_gemm else ()   # the GEMM weight copies, kept current
+        if mirrors and nsq:   # (norm from the reductions' sums of squares; step advanced there)
+            rc = lib.lgx_adam_clip_mirror_sq(*bufs, C.c_void_p(sq), nsq, clip, *adam, *mirrors, stream)
+        elif mirrors:
+            rc = lib.lgx_adam_clip_mirror(*bufs, *norm, *adam, *mirrors, stream)
         else:
-            chk(lib.lgx_adam_clip(_vp(self.flat_p), _vp(self.flat_g), _vp(o.m), _vp(o.v), self.n,
-                                  _vp(self.norm_parts), self.norm_parts.numel(), grad_scale, ppo.max_grad_norm,
-                                  _vp(o.lr_dev), _vp(o.step_dev), o.betas[0], o.betas[1], o.eps, stream), "adam")
+            rc = lib.lgx_adam_clip(*bufs, *norm, *adam, stream)
+        self.check(rc, "adam")
+

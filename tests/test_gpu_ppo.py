@@ -120,6 +120,46 @@ def test_fused_update_single_stream(gpu, monkeypatch):
     assert getattr(fus._fused, "_side", None) is None
 
 
+class _CallCounter:
+    """Forwards every attribute to the product library and counts the calls per entry point (in the
+    style of ppo_trace._LibSpy)."""
+
+    def __init__(self, lib):
+        self._lib, self.calls = lib, {}
+
+    def __getattr__(self, name):
+        fn = getattr(self._lib, name)
+
+        def counted(*args):
+            self.calls[name] = self.calls.get(name, 0) + 1
+            return fn(*args)
+        return counted
+
+
+def test_run_switches_are_read_per_update_call(gpu, monkeypatch):
+    """A run switch (LGX_PPO_DW_SIDE as the side stream's on / off) toggled between update() calls
+    of ONE object takes effect at the next call (tools/kbench.py update_env relies on it): no
+    cross-stream wait with the switch at 0, some with it unset, none again at 0."""
+    monkeypatch.delenv("LGX_PPO_DEV_EVENTS", raising=False)   # (device events: joins go through the library)
+    _, fus = make_pair()
+    f = fus._fused
+    f.lib = spy = _CallCounter(f.lib)
+    waits = []
+    for val in ("0", None, "0"):
+        if val is None:
+            monkeypatch.delenv("LGX_PPO_DW_SIDE", raising=False)
+        else:
+            monkeypatch.setenv("LGX_PPO_DW_SIDE", val)
+        spy.calls.clear()
+        torch.manual_seed(11)
+        losses = fus.update()
+        assert all(torch.isfinite(torch.tensor(losses)))
+        assert spy.calls.get("lgx_adam_clip_mirror_sq", 0) == 8     # 2 epochs x 4 minibatches went through the proxy
+        waits.append(spy.calls.get("lgx_stream_wait_event", 0))
+    torch.cuda.synchronize()
+    assert waits[0] == 0 and waits[1] > 0 and waits[2] == 0, waits
+
+
 def test_reduce_slices_sum_of_squares(gpu):
     """lgx_reduce_slices_sq: the slice sums as lgx_reduce_slices, and per workgroup the sum of squares
     of what it wrote (float4 and scalar jobs), which together give the gradient's squared norm."""

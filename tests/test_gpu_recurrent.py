@@ -51,6 +51,31 @@ def test_recurrent_rollout_heads_on_fused_kernel_match_cpu(gpu):
     assert all(torch.isfinite(p).all() for p in ac_gpu.parameters())
 
 
+def test_recurrent_policy_off_the_gemm_tile_trains_on_autograd(gpu):
+    """Hidden widths that are not multiples of the lgx GEMM's 128-column tile: the fused update has
+    no padded input rows for the memories' outputs, so FusedPPOUpdate.supported refuses the policy
+    and PPO trains it on the autograd update (it used to be accepted and fail inside update())."""
+    from legged_gym_amd.rl.actor_critic import ActorCriticRecurrent
+    from legged_gym_amd.rl.ppo import PPO
+    torch.manual_seed(0)
+    T, N, OBS, ACT = 4, 64, 48, 12
+    ac = ActorCriticRecurrent(OBS, OBS, ACT, [256, 128, 64], [256, 128, 64], rnn_hidden_size=256).to(gpu)
+    ppo = PPO(ac, num_learning_epochs=1, num_mini_batches=2, device=str(gpu))
+    assert ppo._fused is None
+    ppo.init_storage(N, T, [OBS], [None], [ACT])
+    g = torch.Generator(device=gpu).manual_seed(1)
+    with torch.inference_mode():
+        for _ in range(T):
+            obs = torch.randn(N, OBS, device=gpu, generator=g)
+            ppo.act(obs, obs)
+            ppo.process_env_step(torch.randn(N, device=gpu, generator=g),
+                                 torch.rand(N, device=gpu, generator=g) < 0.2, {})
+        ppo.compute_returns(torch.randn(N, OBS, device=gpu, generator=g))
+    vl, sl = ppo.update()
+    assert torch.isfinite(torch.tensor([vl, sl])).all()
+    assert all(torch.isfinite(p).all() for p in ac.parameters())
+
+
 def _recurrent_pair(gpu, T=8, N=512, OBS=48, ACT=12, hidden=(512, 256, 128), rnn=256, cobs=None, epochs=2):
     """Autograd and fused PPO on one ActorCriticRecurrent (deep copies), with identical storage
     filled by a rollout (saved LSTM states, dones mid-rollout) on the autograd one."""

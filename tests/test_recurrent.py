@@ -111,6 +111,25 @@ def test_runner_trains_recurrent_policy_and_exports(tmp_path):
     torch.testing.assert_close(pol(x[0])[0], want[0], atol=1e-5, rtol=1e-5)
 
 
+def test_fused_update_supports_only_policies_it_can_drive(monkeypatch):
+    """FusedPPOUpdate.supported (no GPU needed): a recurrent policy enters the fused update through
+    the padded rows of the lgx GEMM plan only, so hidden widths off the GEMM's 128-column tile, or
+    LGX_PPO_GEMM=lib, leave it on the autograd update; feed-forward policies keep the library path."""
+    from legged_gym_amd.rl.actor_critic import ActorCritic
+    from legged_gym_amd.rl.fused_ppo import FusedPPOUpdate
+    monkeypatch.delenv("LGX_PPO_GEMM", raising=False)
+    monkeypatch.delenv("LGX_PPO_FUSED_RECURRENT", raising=False)
+
+    def rec(hidden):
+        return ActorCriticRecurrent(48, 48, 12, list(hidden), list(hidden), rnn_hidden_size=256)
+    assert not FusedPPOUpdate.supported(rec((256, 128, 64)))
+    assert FusedPPOUpdate.supported(rec((512, 256, 128)))
+    for hidden in ((256, 128, 64), (400, 300)):
+        assert FusedPPOUpdate.supported(ActorCritic(48, 48, 12, list(hidden), list(hidden)))
+    monkeypatch.setenv("LGX_PPO_GEMM", "lib")
+    assert not FusedPPOUpdate.supported(rec((512, 256, 128)))
+
+
 def test_memory_reset_zeroes_done_envs():
     ac = _policy()
     with torch.inference_mode():

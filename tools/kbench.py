@@ -201,7 +201,7 @@ def ppo_ab(T=24, N=4096, OBS=235, ACT=12, modes=("lib", "auto", "lgx", "lib", "a
 
 def update_env_ab(var=os.environ.get("KB_VAR", "LGX_PPO_EARLY_REDUCE"), rounds=int(os.environ.get("KB_ROUNDS", "12")),
                   T=24, N=4096, OBS=235, ACT=12, modes=tuple(os.environ.get("KB_VALUES", "1,0").split(","))):
-    """A/B of an update switch that is read per call / per minibatch (env var `var`, values `modes`),
+    """A/B of an update switch that is read per `update()` call (env var `var`, values `modes`),
     interleaved in ONE process on one PPO object: every round times one full update per value (HIP
     events), so box drift cancels (separate processes on one box drifted by +-5 %); prints median /
     min per value."""
