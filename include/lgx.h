@@ -308,6 +308,48 @@ int lgx_step_from(lgx_sim* sim, const float* actions, int64_t common_step_counte
  * keeps the previous step's tensor alive across env.step(); callers double-buffer with this. */
 int lgx_rebind_obs(lgx_sim* sim, float* obs);
 
+/* Privileged (critic-only) observations of an asymmetric actor-critic, written by the post-physics
+ * launch in the pass that writes obs (lgx_step / lgx_step_from / lgx_post_physics /
+ * lgx_post_physics_fused).  The reference declares the buffer (cfg.env.num_privileged_obs,
+ * base_task.py:75-78), clips it (legged_robot.py:103-106) and returns it from step / reset, but its
+ * compute_observations never fills it: the row layout is this project's own.
+ *   row = [clean | tail], `width` floats, rows packed (no alignment requirement)
+ *   clean [0, num_obs): the observation row before noise, clampf((v - sub) * mul, +-clip_obs);
+ *                       no draws of its own
+ *   tail: term t at [term_offsets[t], + its width), every entry clipped to +-clip_obs, from the
+ *         values the same launch's obs are computed from (reset envs: this step's contact forces
+ *         and torques) */
+#define LGX_MAX_PRIV_OBS 512        /* the rollout MLP's input limit (lgx_mlp_x3_desc dims) */
+#define LGX_PRIV_MAX_TERMS 8
+enum lgx_priv_term {
+  LGX_PRIV_FRICTION = 0,    /* 1: friction[e] */
+  LGX_PRIV_BASE_MASS,       /* 1: body_mass_scale[e][0] */
+  LGX_PRIV_MASS_SCALE,      /* LGX_NUM_DYN: body_mass_scale[e][:] */
+  LGX_PRIV_FEET_CONTACT,    /* num_feet: contact_forces[e][feet[f]][2] > 1 ? 1 : 0 (_reward_feet_air_time's
+                               threshold, legged_robot.py:943) */
+  LGX_PRIV_FEET_FORCES,     /* 3 num_feet: contact_forces[e][feet[f]][:] * contact_force_scale */
+  LGX_PRIV_TORQUES,         /* LGX_NUM_DOF: torques[e][:] * torque_scale */
+  LGX_PRIV_COUNT
+};
+typedef struct lgx_priv_obs_desc {
+  int32_t width;                              /* floats per row: num_obs <= width <= LGX_MAX_PRIV_OBS */
+  int32_t num_terms;                          /* tail terms, <= LGX_PRIV_MAX_TERMS */
+  int32_t term_ids[LGX_PRIV_MAX_TERMS];       /* enum lgx_priv_term */
+  int32_t term_offsets[LGX_PRIV_MAX_TERMS];   /* first column of each term: >= num_obs, disjoint, in the row */
+  float contact_force_scale, torque_scale;
+} lgx_priv_obs_desc;
+/* Bind the output (device float[N, desc->width]) and its layout for the next calls; buf == NULL
+ * unbinds (desc is then ignored and the launches are the ones of a sim that never bound a row).
+ * LGX_EINVAL (message in lgx_last_error) for a null sim or desc, a width outside
+ * [num_obs, LGX_MAX_PRIV_OBS], more than LGX_PRIV_MAX_TERMS terms, an unknown term id, a term
+ * that overlaps the clean part or another term or leaves the row, or a friction term without a
+ * bound friction buffer. */
+int lgx_bind_privileged_obs(lgx_sim* sim, float* buf, const lgx_priv_obs_desc* desc);
+/* Re-point the bound row output, layout unchanged (callers double-buffer it as they do obs:
+ * rsl_rl copies the critic observations into its storage after env.step).  LGX_EINVAL for a null
+ * argument or a sim with no row bound. */
+int lgx_rebind_privileged_obs(lgx_sim* sim, float* buf);
+
 /* Data-parallel gradient all-reduce over RCCL (SURVEY §8(b) lgx_allreduce_grads; §8(e): the
  * gradient average of a multi-GPU PPO update, one rank per GPU).  One communicator per rank,
  * created collectively from a unique id that rank 0 draws and the caller distributes (e.g. over

@@ -43,6 +43,7 @@ struct lgx_sim {
   lgx_env_params* d_params;
   const float* draws;
   float* extras_snapshot;  // lgx_rebind_extras (NULL: no per-call copy)
+  lgx_priv_args priv;      // lgx_bind_privileged_obs (buf NULL: no privileged row)
   // Go1 actuator net off the critical path: its output (dVel) is not read by the step
   // (go1.py:71-73), so it runs on an auxiliary stream concurrently with post-physics and the
   // next policy forward; the next physics launch (which rewrites model_ins) waits for it.
@@ -202,6 +203,7 @@ int lgx_sim_create(const lgx_model* model, const lgx_env_params* params, const l
   s->bufs = *bufs;
   s->draws = nullptr;
   s->extras_snapshot = nullptr;
+  s->priv = lgx_priv_args{};
   s->aux = nullptr;
   s->aux_in = s->aux_done = nullptr;
   s->aux_pending = false;
@@ -293,6 +295,65 @@ int lgx_rebind_obs(lgx_sim* s, float* obs) {
   return 0;
 }
 
+int lgx_bind_privileged_obs(lgx_sim* s, float* buf, const lgx_priv_obs_desc* d) {
+  if (!s) return fail(LGX_EINVAL, "lgx_bind_privileged_obs: null sim");
+  if (!buf) {
+    s->priv = lgx_priv_args{};
+    return 0;
+  }
+  if (!d) return fail(LGX_EINVAL, "lgx_bind_privileged_obs: null desc");
+  const lgx_env_params& p = s->params;
+  if (d->width < p.num_obs) return fail(LGX_EINVAL, "lgx_bind_privileged_obs: width is below num_obs");
+  if (d->width > LGX_MAX_PRIV_OBS) return fail(LGX_EINVAL, "lgx_bind_privileged_obs: width is above LGX_MAX_PRIV_OBS");
+  if (d->num_terms < 0 || d->num_terms > LGX_PRIV_MAX_TERMS)
+    return fail(LGX_EINVAL, "lgx_bind_privileged_obs: bad num_terms");
+  lgx_priv_args a{};
+  int32_t beg[LGX_PRIV_MAX_TERMS], end[LGX_PRIV_MAX_TERMS];
+  for (int t = 0; t < d->num_terms; ++t) {
+    const int id = d->term_ids[t];
+    int w;
+    switch (id) {
+      case LGX_PRIV_FRICTION: case LGX_PRIV_BASE_MASS: w = 1; break;
+      case LGX_PRIV_MASS_SCALE: w = LGX_NUM_DYN; break;
+      case LGX_PRIV_FEET_CONTACT: w = p.num_feet; break;
+      case LGX_PRIV_FEET_FORCES: w = 3 * p.num_feet; break;
+      case LGX_PRIV_TORQUES: w = LGX_NUM_DOF; break;
+      default: return fail(LGX_EINVAL, "lgx_bind_privileged_obs: unknown term id");
+    }
+    if (id == LGX_PRIV_FRICTION && !s->bufs.friction)
+      return fail(LGX_EINVAL, "lgx_bind_privileged_obs: the friction term needs a bound friction buffer");
+    if (id == LGX_PRIV_FEET_CONTACT || id == LGX_PRIV_FEET_FORCES) {
+      // the kernel reads the feet's rows of the staged [LGX_MAX_BODIES, 3] contact forces
+      if (p.num_feet < 0 || p.num_feet > 4) return fail(LGX_EINVAL, "lgx_bind_privileged_obs: bad num_feet");
+      for (int f = 0; f < p.num_feet; ++f)
+        if (p.feet_indices[f] < 0 || p.feet_indices[f] >= LGX_MAX_BODIES)
+          return fail(LGX_EINVAL, "lgx_bind_privileged_obs: a foot index is outside the contact-force rows");
+    }
+    const int off = d->term_offsets[t];
+    if (off < p.num_obs || off > d->width - w)
+      return fail(LGX_EINVAL, "lgx_bind_privileged_obs: a term lies outside the tail of the row");
+    for (int u = 0; u < t; ++u)
+      if (off < end[u] && beg[u] < off + w) return fail(LGX_EINVAL, "lgx_bind_privileged_obs: terms overlap");
+    a.set(t, id, off);
+    beg[t] = off;
+    end[t] = off + w;
+  }
+  a.buf = buf;
+  a.width = d->width;
+  a.num_terms = d->num_terms;
+  a.cf_scale = d->contact_force_scale;
+  a.tq_scale = d->torque_scale;
+  s->priv = a;
+  return 0;
+}
+
+int lgx_rebind_privileged_obs(lgx_sim* s, float* buf) {
+  if (!s || !buf) return fail(LGX_EINVAL, "lgx_rebind_privileged_obs: null argument");
+  if (!s->priv.buf) return fail(LGX_EINVAL, "lgx_rebind_privileged_obs: no privileged row is bound");
+  s->priv.buf = buf;
+  return 0;
+}
+
 int lgx_rebind_extras(lgx_sim* s, float* snapshot) {
   if (!s) return fail(LGX_EINVAL, "lgx_rebind_extras: null sim");
   s->extras_snapshot = snapshot;
@@ -341,7 +402,7 @@ int lgx_ground_contact(lgx_sim* s, const float* points, int32_t n, float* out, v
 int lgx_post_physics(lgx_sim* s, int64_t step, void* stream) {
   if (!s) return fail(LGX_EINVAL, "lgx_post_physics: null sim");
   return launch_check(lgx_launch_post_physics(s->d_params, s->bufs, s->params.num_envs, s->params.num_obs, s->n_term_rows,
-                                              s->params.measure_heights, step, s->draws, s->extras_snapshot,
+                                              s->params.measure_heights, step, s->draws, s->extras_snapshot, s->priv,
                                               (hipStream_t)stream),
                       "lgx_post_physics: launch");
 }
@@ -379,7 +440,7 @@ static int post_physics_fused(lgx_sim* s, int64_t step, hipStream_t st, bool sam
     rc = launch_check(lgx_launch_post_physics_act(s->d_params, s->bufs, p.num_envs, step, s->draws, s->extras_snapshot,
                                                   s->bufs.model_ins, s->bufs.act_dvel,
                                                   (int64_t)p.decimation * p.num_envs * 4, s->bufs.act_net_w,
-                                                  s->bufs.act_net_scale, st),
+                                                  s->bufs.act_net_scale, s->priv, st),
                       "lgx_step: post-physics + actuator launch");
     lgx_timing = lgx_timing_slot{};
     return rc;

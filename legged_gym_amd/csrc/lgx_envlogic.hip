@@ -287,9 +287,53 @@ LGX_DEV bool take_last_ticket(const lgx_buffers& B, int nblocks) {
   return last;
 }
 
-// one post-physics workgroup: envs [blk * LGX_ENV_BLOCK, +LGX_ENV_BLOCK) of nblocks
+// The clean (noise-free) entry of a privileged row next to the noisy obs entry: the same rounded
+// product (d * mul), taken from an opaque copy of d so that it is a value of its own.  Were it the
+// obs expression's product, that product would have two uses, and which of the two multiplies of
+// `d * mul + noise * scale` the compiler contracts into the add could then differ from the
+// instantiation without a privileged row - whose obs must stay bitwise what they were.
+LGX_DEV float priv_clean(float d, float mul) {
+  asm("" : "+v"(d));
+  return d * mul;
+}
+
+// the tail terms of the privileged rows of one workgroup's envs (lgx.h, enum lgx_priv_term), from
+// the rows phase C reads: srow (torques at 24, contact forces at 36: this step's, also for reset
+// envs) and one global load per entry for friction / body_mass_scale
+template <int SROW1>
+LGX_DEV void priv_tail(const lgx_env_params* __restrict__ P, const lgx_buffers& B, const lgx_priv_args& pv,
+                       const float (*srow)[SROW1], int e0) {
+  const int N = P->num_envs, tid = threadIdx.x, nf = P->num_feet;
+  const float clip = P->clip_obs;
+  for (int t = 0; t < pv.num_terms; ++t) {
+    const int id = pv.id(t), off = pv.off(t);
+    const int w = id == LGX_PRIV_MASS_SCALE ? LGX_NUM_DYN : id == LGX_PRIV_FEET_CONTACT ? nf
+                : id == LGX_PRIV_FEET_FORCES ? 3 * nf : id == LGX_PRIV_TORQUES ? LGX_NUM_DOF : 1;
+    for (int idx = tid; idx < LGX_ENV_BLOCK * w; idx += ENV_THREADS) {
+      const int le = idx / w, k = idx - le * w;
+      const int e = e0 + le;
+      if (e >= N) break;
+      float v;
+      switch (id) {
+        case LGX_PRIV_FRICTION: v = B.friction[e]; break;
+        case LGX_PRIV_BASE_MASS: v = B.body_mass_scale[(int64_t)e * LGX_NUM_DYN]; break;
+        case LGX_PRIV_MASS_SCALE: v = B.body_mass_scale[(int64_t)e * LGX_NUM_DYN + k]; break;
+        case LGX_PRIV_FEET_CONTACT: v = srow[le][36 + 3 * P->feet_indices[k] + 2] > 1.f ? 1.f : 0.f; break;
+        case LGX_PRIV_FEET_FORCES: v = srow[le][36 + 3 * P->feet_indices[k / 3] + k % 3] * pv.cf_scale; break;
+        default: v = srow[le][24 + k] * pv.tq_scale; break;   // LGX_PRIV_TORQUES
+      }
+      pv.buf[(int64_t)e * pv.width + off + k] = clampf(v, -clip, clip);
+    }
+  }
+}
+
+// one post-physics workgroup: envs [blk * LGX_ENV_BLOCK, +LGX_ENV_BLOCK) of nblocks.  PRIV: also
+// the privileged rows (pv; lgx_bind_privileged_obs) - compiled apart, so that the instantiation a
+// sim without a bound row launches carries none of it
+template <bool PRIV>
 LGX_DEV void post_physics_body(const lgx_env_params* __restrict__ P, const lgx_buffers& B, int64_t step,
-                               const float* draws, int blk, int nblocks, float* snapshot) {
+                               const float* draws, int blk, int nblocks, float* snapshot,
+                               const lgx_priv_args& pv) {
   const int N = P->num_envs;
   const int nobs = P->num_obs;
   const int e0 = blk * LGX_ENV_BLOCK;
@@ -567,6 +611,8 @@ LGX_DEV void post_physics_body(const lgx_env_params* __restrict__ P, const lgx_b
       const int so = src_off[i];
       const float v = so < 16 ? sbase[le][so] : srow[le][so - 16];   // (reference order, :216-226)
       float o = (v - obs_sub[i]) * obs_mul[i];
+      if constexpr (PRIV)
+        pv.buf[(int64_t)e * pv.width + i] = clampf(priv_clean(v - obs_sub[i], obs_mul[i]), -clip, clip);
       if (noise) o += (2.f * nz[u] - 1.f) * obs_nsc[i];
       B.obs[(int64_t)e * nobs + i] = clampf(o, -clip, clip);
     }
@@ -586,10 +632,13 @@ LGX_DEV void post_physics_body(const lgx_env_params* __restrict__ P, const lgx_b
       if (i >= nobs) break;
       const float v = clampf(z - sheight[le][i - 48], -1.f, 1.f);
       float o = (v - obs_sub[i]) * obs_mul[i];
+      if constexpr (PRIV)
+        pv.buf[(int64_t)e * pv.width + i] = clampf(priv_clean(v - obs_sub[i], obs_mul[i]), -clip, clip);
       if (noise) o += (2.f * nz[u] - 1.f) * obs_nsc[i];
       B.obs[(int64_t)e * nobs + i] = clampf(o, -clip, clip);
     }
   }
+  if constexpr (PRIV) priv_tail(P, B, pv, srow, e0);
   LGX_CLK(4);
   // ---- last_* copies (:136-138), post-reset values
   for (int idx = tid; idx < LGX_ENV_BLOCK * 12; idx += ENV_THREADS) {
@@ -615,7 +664,14 @@ LGX_DEV void post_physics_body(const lgx_env_params* __restrict__ P, const lgx_b
 __global__ void __launch_bounds__(ENV_THREADS)
 lgx_post_physics_kernel(const lgx_env_params* __restrict__ P, lgx_buffers B, int64_t step, const float* draws,
                         float* snapshot) {
-  post_physics_body(P, B, step, draws, blockIdx.x, gridDim.x, snapshot);
+  post_physics_body<false>(P, B, step, draws, blockIdx.x, gridDim.x, snapshot, lgx_priv_args{});
+}
+
+// the same with a privileged row bound
+__global__ void __launch_bounds__(ENV_THREADS)
+lgx_post_physics_priv_kernel(const lgx_env_params* __restrict__ P, lgx_buffers B, int64_t step, const float* draws,
+                             float* snapshot, lgx_priv_args pv) {
+  post_physics_body<true>(P, B, step, draws, blockIdx.x, gridDim.x, snapshot, pv);
 }
 
 // post-physics and the Go1 actuator network in ONE launch: workgroups [0, nblocks) are the
@@ -626,7 +682,16 @@ lgx_post_physics_kernel(const lgx_env_params* __restrict__ P, lgx_buffers B, int
 __global__ void __launch_bounds__(ENV_THREADS, 2)
 lgx_post_physics_act_kernel(const lgx_env_params* __restrict__ P, lgx_buffers B, int64_t step, const float* draws,
                             float* snapshot, WsArgs wa, int32_t nblocks) {
-  if ((int)blockIdx.x < nblocks) post_physics_body(P, B, step, draws, blockIdx.x, nblocks, snapshot);
+  if ((int)blockIdx.x < nblocks)
+    post_physics_body<false>(P, B, step, draws, blockIdx.x, nblocks, snapshot, lgx_priv_args{});
+  else actuator_ws_body(wa, blockIdx.x - nblocks, gridDim.x - nblocks);
+}
+
+// the same with a privileged row bound (still two workgroups per CU)
+__global__ void __launch_bounds__(ENV_THREADS, 2)
+lgx_post_physics_act_priv_kernel(const lgx_env_params* __restrict__ P, lgx_buffers B, int64_t step, const float* draws,
+                                 float* snapshot, WsArgs wa, int32_t nblocks, lgx_priv_args pv) {
+  if ((int)blockIdx.x < nblocks) post_physics_body<true>(P, B, step, draws, blockIdx.x, nblocks, snapshot, pv);
   else actuator_ws_body(wa, blockIdx.x - nblocks, gridDim.x - nblocks);
 }
 
@@ -664,17 +729,22 @@ lgx_extras_finalize_kernel(const lgx_env_params* __restrict__ P, lgx_buffers B, 
 
 int lgx_launch_post_physics(const lgx_env_params* dp, const lgx_buffers& b, int32_t n_envs, int32_t num_obs,
                             int32_t n_term_rows, int32_t measure_heights, int64_t step, const float* draws,
-                            float* extras_snapshot, hipStream_t stream) {
+                            float* extras_snapshot, const lgx_priv_args& pv, hipStream_t stream) {
   (void)num_obs; (void)n_term_rows; (void)measure_heights;
   int blocks = (n_envs + LGX_ENV_BLOCK - 1) / LGX_ENV_BLOCK;
-  LGX_LAUNCH(lgx_post_physics_kernel, dim3(blocks), dim3(ENV_THREADS), 0, stream, dp, b, step, draws,
-             extras_snapshot);
+  if (pv.buf)
+    LGX_LAUNCH(lgx_post_physics_priv_kernel, dim3(blocks), dim3(ENV_THREADS), 0, stream, dp, b, step, draws,
+               extras_snapshot, pv);
+  else
+    LGX_LAUNCH(lgx_post_physics_kernel, dim3(blocks), dim3(ENV_THREADS), 0, stream, dp, b, step, draws,
+               extras_snapshot);
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
 int lgx_launch_post_physics_act(const lgx_env_params* dp, const lgx_buffers& b, int32_t n_envs, int64_t step,
                                 const float* draws, float* extras_snapshot, const float* act_in, float* act_out,
-                                int64_t act_rows, const float* act_w, const float* act_scale, hipStream_t stream) {
+                                int64_t act_rows, const float* act_w, const float* act_scale,
+                                const lgx_priv_args& pv, hipStream_t stream) {
   static_assert(ENV_THREADS == 256, "the actuator-net workgroups are 256 threads");
   const int blocks = (n_envs + LGX_ENV_BLOCK - 1) / LGX_ENV_BLOCK;
   const int64_t tiles = (act_rows + WS_BM - 1) / WS_BM;
@@ -683,8 +753,12 @@ int lgx_launch_post_physics_act(const lgx_env_params* dp, const lgx_buffers& b, 
   // one persistent actuator workgroup per CU next to the post-physics workgroups
   const int act_wgs = (int)std::max<int64_t>(1, std::min<int64_t>(tiles, cus));
   WsArgs wa{act_in, act_out, act_rows, act_w, act_scale};
-  LGX_LAUNCH(lgx_post_physics_act_kernel, dim3(blocks + act_wgs), dim3(ENV_THREADS), 0, stream, dp, b, step, draws,
-             extras_snapshot, wa, blocks);
+  if (pv.buf)
+    LGX_LAUNCH(lgx_post_physics_act_priv_kernel, dim3(blocks + act_wgs), dim3(ENV_THREADS), 0, stream, dp, b, step,
+               draws, extras_snapshot, wa, blocks, pv);
+  else
+    LGX_LAUNCH(lgx_post_physics_act_kernel, dim3(blocks + act_wgs), dim3(ENV_THREADS), 0, stream, dp, b, step, draws,
+               extras_snapshot, wa, blocks);
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 

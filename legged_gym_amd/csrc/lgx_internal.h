@@ -30,13 +30,35 @@ int lgx_launch_physics(const lgx_dev_model* dm, const lgx_env_params* dp, const 
 int lgx_launch_physics_dense(const lgx_dev_model* dm, const lgx_env_params* dp, const lgx_buffers& b, int32_t n_envs,
                              int32_t nsub, int32_t from_actions, const float* act_src, hipStream_t stream,
                              int32_t frozen, int32_t num_points);
+// the privileged-observation row of a sim (lgx_bind_privileged_obs, checked there), passed by value
+// to the post-physics launches; buf == nullptr: nothing bound.  Term t's id is 4 bits and its first
+// column 16 bits of packed words, not arrays: a kernel argument indexed by a loop variable is kept
+// in scratch memory.
+struct lgx_priv_args {
+  float* buf;            // [N, width]
+  int32_t width, num_terms;
+  uint32_t ids;          // term t: bits [4t, 4t + 4)
+  uint32_t pad;
+  uint64_t offs_lo, offs_hi;   // term t < 4: bits [16t, 16t + 16) of offs_lo; else of offs_hi, t - 4
+  float cf_scale, tq_scale;
+  __host__ __device__ int id(int t) const { return (int)((ids >> (4 * t)) & 15u); }
+  __host__ __device__ int off(int t) const { return (int)(((t < 4 ? offs_lo : offs_hi) >> (16 * (t & 3))) & 0xffffu); }
+  void set(int t, int id_, int off_) {
+    ids |= (uint32_t)id_ << (4 * t);
+    (t < 4 ? offs_lo : offs_hi) |= (uint64_t)off_ << (16 * (t & 3));
+  }
+};
+static_assert(LGX_PRIV_MAX_TERMS <= 8 && LGX_PRIV_COUNT <= 16 && LGX_MAX_PRIV_OBS < 65536, "lgx_priv_args packing");
+// pv.buf == nullptr launches the kernels of a sim without a privileged row (no other kernel argument
+// or code); otherwise their privileged instantiations
 int lgx_launch_post_physics(const lgx_env_params* dp, const lgx_buffers& b, int32_t n_envs, int32_t num_obs,
                             int32_t n_term_rows, int32_t measure_heights, int64_t step, const float* draws,
-                            float* extras_snapshot, hipStream_t stream);
+                            float* extras_snapshot, const lgx_priv_args& pv, hipStream_t stream);
 // post-physics + the Go1 actuator net (act_rows rows of act_in -> act_out) in one launch
 int lgx_launch_post_physics_act(const lgx_env_params* dp, const lgx_buffers& b, int32_t n_envs, int64_t step,
                                 const float* draws, float* extras_snapshot, const float* act_in, float* act_out,
-                                int64_t act_rows, const float* act_w, const float* act_scale, hipStream_t stream);
+                                int64_t act_rows, const float* act_w, const float* act_scale,
+                                const lgx_priv_args& pv, hipStream_t stream);
 int lgx_launch_reset_idx(const lgx_env_params* dp, const lgx_buffers& b, int32_t n_envs, int32_t n_term_rows,
                          const int32_t* ids, int32_t n, int64_t step, int32_t init_done, const float* draws,
                          float* extras_snapshot, hipStream_t stream);

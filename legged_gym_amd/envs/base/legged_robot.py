@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from legged_gym_amd import LEGGED_GYM_ROOT_DIR
+from legged_gym_amd.envs.base import privileged
 from legged_gym_amd.envs.base.base_task import BaseTask
 from legged_gym_amd.sim import abi
 from legged_gym_amd.sim.model import RobotAsset, build_model, resolve_asset_path
@@ -77,6 +78,23 @@ class LgxBackend:
 
     def rebind_obs(self, obs):
         self._check(self.lib.lgx_rebind_obs(self.handle, C.c_void_p(obs.data_ptr())), "lgx_rebind_obs")
+
+    def bind_privileged_obs(self, buf, layout, contact_force_scale, torque_scale):
+        """lgx_bind_privileged_obs: the row output and its layout (envs/base/privileged.py); None unbinds."""
+        if buf is None:
+            self._check(self.lib.lgx_bind_privileged_obs(self.handle, None, None), "lgx_bind_privileged_obs")
+            return
+        d = abi.LgxPrivObsDesc()
+        d.width, d.num_terms = layout.width, len(layout.terms)
+        for t, (_, tid, sl) in enumerate(layout.terms):
+            d.term_ids[t], d.term_offsets[t] = tid, sl.start
+        d.contact_force_scale, d.torque_scale = contact_force_scale, torque_scale
+        self._check(self.lib.lgx_bind_privileged_obs(self.handle, C.c_void_p(buf.data_ptr()), C.byref(d)),
+                    "lgx_bind_privileged_obs")
+
+    def rebind_privileged_obs(self, buf):
+        self._check(self.lib.lgx_rebind_privileged_obs(self.handle, C.c_void_p(buf.data_ptr())),
+                    "lgx_rebind_privileged_obs")
 
     def sync_aux(self):
         self._check(self.lib.lgx_sync_aux(self.handle, self.stream()), "lgx_sync_aux")
@@ -177,6 +195,10 @@ class LeggedRobot(BaseTask):
         if hasattr(self._backend, "rebind_obs"):
             self._backend.rebind_obs(ob)
         self.obs_buf = ob
+        if self._priv_bufs is not None:    # the critic's row likewise: storage copies it after env.step
+            pb = self._priv_bufs[self._obs_slot]
+            self._backend.rebind_privileged_obs(pb)
+            self.privileged_obs_buf = pb
 
     def compute_observations(self):
         raise NotImplementedError("observations are produced inside lgx_step/lgx_post_physics")
@@ -561,7 +583,36 @@ class LeggedRobot(BaseTask):
         self._lgx_params, self._lgx_bufs = p, b
         self._obs_bufs = [self.obs_buf, torch.zeros_like(self.obs_buf)]
         self._obs_slot = 0
+        layout = self._privileged_layout()
         self._backend = self._make_backend(self._lgx_model, p, b)
+        self._bind_privileged_obs(layout)
+
+    def _privileged_layout(self):
+        """The critic's row `[clean obs | cfg.privileged.terms]` (envs/base/privileged.py), or None
+        without env.num_privileged_obs; ValueError for a config that does not add up."""
+        pcfg = getattr(self.cfg, "privileged", None)
+        terms = tuple(getattr(pcfg, "terms", ()))
+        if self.num_privileged_obs is None:
+            if terms:
+                raise ValueError(f"privileged.terms = {terms} but env.num_privileged_obs is None: set it to "
+                                 "num_observations + the terms' width")
+            return None
+        return privileged.layout(terms, self.num_obs, len(self.feet_indices), self.num_privileged_obs)
+
+    def _bind_privileged_obs(self, layout):
+        """Bind the two alternating privileged rows to the kernels (lgx_bind_privileged_obs)."""
+        self.privileged_layout, self._priv_bufs = layout, None
+        if layout is None:
+            return
+        if not hasattr(self._backend, "bind_privileged_obs"):
+            raise ValueError(f"env.num_privileged_obs = {self.num_privileged_obs}: the backend "
+                             f"{type(self._backend).__name__} cannot bind a privileged observation buffer (the "
+                             "CPU oracle backend of the tests has no privileged row; the lgx backend writes it)")
+        pcfg = getattr(self.cfg, "privileged", None)
+        self._priv_bufs = [self.privileged_obs_buf, torch.zeros_like(self.privileged_obs_buf)]
+        self._backend.bind_privileged_obs(self._priv_bufs[self._obs_slot], layout,
+                                          float(getattr(pcfg, "contact_force_scale", 0.01)),
+                                          float(getattr(pcfg, "torque_scale", 0.05)))
 
     def _trimesh_contact_table(self):
         """mesh_type 'trimesh' with a slope threshold: the contact table of the slope-corrected mesh

@@ -150,6 +150,15 @@ class LeggedRobotCfg(BaseConfig):
             gravity = 0.05
             height_measurements = 0.1
 
+    class privileged:
+        """The critic's row when env.num_privileged_obs is set (no reference counterpart: the
+        reference never fills the buffer).  Row = the observations before noise, then `terms` in
+        order (envs/base/privileged.py: friction, base_mass, mass_scale, feet_contact, feet_forces,
+        torques); num_privileged_obs must equal num_observations + the terms' width."""
+        terms = ()
+        contact_force_scale = 0.01
+        torque_scale = 0.05
+
     class viewer:  # ref :190-194
         ref_env = 0
         pos = [10, 0, 6]

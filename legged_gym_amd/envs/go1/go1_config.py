@@ -3,6 +3,8 @@
 `Go1RoughCfg` is the reference's Go1 config (despite the name: flat `plane`, 48-dim obs).
 `Go1RoughTerrainCfg` is BASELINE config C3/C4: the same robot on the curriculum trimesh
 with the 187-point height scan (235-dim obs), as SURVEY.md §8 defines it.
+`Go1RoughAsymCfg` is that task with an asymmetric actor-critic: the critic reads the privileged
+row (noise-free observations + the randomised friction / base mass + foot contacts).
 """
 from legged_gym_amd.envs.base.legged_robot_config import LeggedRobotCfg, LeggedRobotCfgPPO
 
@@ -84,3 +86,18 @@ class Go1RoughTerrainCfg(Go1RoughCfg):
     class terrain(Go1RoughCfg.terrain):
         mesh_type = 'trimesh'
         measure_heights = True
+
+
+class Go1RoughAsymCfg(Go1RoughTerrainCfg):
+    """go1_rough with a privileged critic (no reference counterpart): the actor sees the noisy 235
+    observations, the critic the same 235 before noise plus friction, base mass scale, foot contact
+    flags and scaled foot contact forces (1 + 1 + 4 + 12 = 18)."""
+    class env(Go1RoughTerrainCfg.env):
+        num_privileged_obs = 253
+
+    class privileged(Go1RoughTerrainCfg.privileged):
+        terms = ("friction", "base_mass", "feet_contact", "feet_forces")
+
+    class domain_rand(Go1RoughTerrainCfg.domain_rand):
+        randomize_friction = True
+        randomize_base_mass = True

@@ -149,6 +149,17 @@ class LgxCopy2dJob(C.Structure):
                 ("dst_bs", i64), ("rows", i32), ("cols", i32), ("batch", i32), ("transpose", i32)]
 
 
+MAX_PRIV_OBS = 512        # LGX_MAX_PRIV_OBS
+PRIV_MAX_TERMS = 8        # LGX_PRIV_MAX_TERMS
+# enum lgx_priv_term keyed by the names of cfg.privileged.terms (envs/base/privileged.py holds the widths)
+PRIV_TERM_IDS = {"friction": 0, "base_mass": 1, "mass_scale": 2, "feet_contact": 3, "feet_forces": 4, "torques": 5}
+
+
+class LgxPrivObsDesc(C.Structure):
+    _fields_ = [("width", i32), ("num_terms", i32), ("term_ids", i32 * PRIV_MAX_TERMS),
+                ("term_offsets", i32 * PRIV_MAX_TERMS), ("contact_force_scale", f32), ("torque_scale", f32)]
+
+
 PPO_MAX_ACTIONS = 16
 MAX_REDUCE_JOBS = 16
 EPISODE_RING_MAX = 4096   # LGX_EPISODE_RING_MAX: largest ring of lgx_episode_stats_step
@@ -196,6 +207,8 @@ def declare(lib, prefix="lgx"):
             "ground_contact": (C.c_int, [vp, vp, i32, vp, vp]),
             "sync_aux": (C.c_int, [vp, vp]),
             "rebind_extras": (C.c_int, [vp, vp]),
+            "bind_privileged_obs": (C.c_int, [vp, vp, C.POINTER(LgxPrivObsDesc)]),
+            "rebind_privileged_obs": (C.c_int, [vp, vp]),
             "sim_buffer": (C.c_int, [vp, i32, C.POINTER(vp), C.POINTER(i64), C.POINTER(i32), C.POINTER(i32)]),
             "ppo_gather_rows": (C.c_int, [vp, vp, vp, i64, i32, vp]),
             "ppo_act": (C.c_int, [C.POINTER(LgxPpoActArgs), vp]),
@@ -257,7 +270,7 @@ def declare(lib, prefix="lgx"):
 
 
 EXPORTED = ["lgx_last_error", "lgx_version", "lgx_physics_lane_split", "lgx_trimesh_build", "lgx_struct_sizes", "lgx_scratch_floats", "lgx_sim_create",
-            "lgx_sim_destroy", "lgx_step", "lgx_simulate", "lgx_post_physics", "lgx_post_physics_fused", "lgx_reset_idx", "lgx_set_draws", "lgx_rebind_obs", "lgx_rebind_extras", "lgx_sim_buffer", "lgx_step_from", "lgx_drive_inputs", "lgx_ground_contact", "lgx_sync_aux",
+            "lgx_sim_destroy", "lgx_step", "lgx_simulate", "lgx_post_physics", "lgx_post_physics_fused", "lgx_reset_idx", "lgx_set_draws", "lgx_rebind_obs", "lgx_rebind_extras", "lgx_bind_privileged_obs", "lgx_rebind_privileged_obs", "lgx_sim_buffer", "lgx_step_from", "lgx_drive_inputs", "lgx_ground_contact", "lgx_sync_aux",
             "lgx_actuator_mlp", "lgx_actuator_lstm", "lgx_mlp_forward", "lgx_gae", "lgx_gae_norm_scratch", "lgx_gae_norm", "lgx_gae_parts", "lgx_adv_norm",
             "lgx_profile_enable", "lgx_profile_collect", "lgx_mlp_forward_batch",
             "lgx_ppo_gather_rows", "lgx_bias_act", "lgx_ppo_loss_partials_floats", "lgx_ppo_loss", "lgx_ppo_adapt_lr",

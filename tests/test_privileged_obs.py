@@ -1,0 +1,194 @@
+"""CPU: the privileged observation row's layout, config surface, C-ABI declarations and the torch
+reference the GPU tests compare the kernel with (tests/privileged_obs_ref.py).  The reference
+project never fills its privileged buffer: the layout checked here is this project's own."""
+import ctypes as C
+import os
+import re
+import types
+
+import numpy as np
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ALL_TERMS = ("friction", "base_mass", "mass_scale", "feet_contact", "feet_forces", "torques")
+
+
+def test_layout_slices_quadruped_and_biped():
+    from legged_gym_amd.envs.base.privileged import layout
+    quad = layout(ALL_TERMS, 48, 4)
+    assert quad.clean == slice(0, 48)
+    assert quad.slices() == {"friction": slice(48, 49), "base_mass": slice(49, 50), "mass_scale": slice(50, 63),
+                             "feet_contact": slice(63, 67), "feet_forces": slice(67, 79), "torques": slice(79, 91)}
+    assert quad.width == 91 and quad.tail_width == 43
+    assert [tid for _, tid, _ in quad.terms] == [0, 1, 2, 3, 4, 5]      # enum lgx_priv_term
+    cassie = layout(("feet_forces", "feet_contact", "torques"), 235, 2)   # two feet; any order
+    assert cassie.slices() == {"feet_forces": slice(235, 241), "feet_contact": slice(241, 243),
+                               "torques": slice(243, 255)}
+    assert cassie.width == 255
+    empty = layout((), 235, 4, num_privileged_obs=235)      # the clean observations alone
+    assert empty.width == 235 and empty.terms == []
+
+
+def test_layout_rejects_bad_configs():
+    from legged_gym_amd.envs.base.privileged import layout
+    with pytest.raises(ValueError, match="unknown privileged observation term 'frictoin'"):
+        layout(("frictoin",), 48, 4)
+    with pytest.raises(ValueError, match="listed twice"):
+        layout(("friction", "torques", "friction"), 48, 4)
+    with pytest.raises(ValueError, match="num_privileged_obs = 252"):
+        layout(("friction", "base_mass", "feet_contact", "feet_forces"), 235, 4, num_privileged_obs=252)
+    assert layout(("torques",), 500, 4).width == 512                     # the limit itself is allowed
+    with pytest.raises(ValueError, match="limit is 512"):
+        layout(("torques",), 501, 4)
+
+
+def test_go1_rough_asym_is_registered_with_a_253_wide_row():
+    import legged_gym_amd.envs  # noqa: F401
+    from legged_gym_amd.envs.base.legged_robot_config import LeggedRobotCfg
+    from legged_gym_amd.envs.base.privileged import layout
+    from legged_gym_amd.envs.go1.go1 import Go1
+    from legged_gym_amd.envs.go1.go1_config import Go1RoughCfgPPO, Go1RoughTerrainCfg
+    from legged_gym_amd.utils.task_registry import task_registry
+    assert task_registry.get_task_class("go1_rough_asym") is Go1
+    env_cfg, train_cfg = task_registry.get_cfgs("go1_rough_asym")
+    assert isinstance(env_cfg, Go1RoughTerrainCfg) and isinstance(train_cfg, Go1RoughCfgPPO)
+    assert env_cfg.privileged.terms == ("friction", "base_mass", "feet_contact", "feet_forces")
+    assert env_cfg.domain_rand.randomize_friction and env_cfg.domain_rand.randomize_base_mass
+    lay = layout(env_cfg.privileged.terms, env_cfg.env.num_observations, 4, env_cfg.env.num_privileged_obs)
+    assert lay.width == env_cfg.env.num_privileged_obs == 253 == 235 + 18
+    # the defaults leave every other task without a privileged row
+    d = LeggedRobotCfg()
+    assert d.privileged.terms == () and d.env.num_privileged_obs is None
+    assert (d.privileged.contact_force_scale, d.privileged.torque_scale) == (0.01, 0.05)
+    for name in task_registry.task_classes:
+        if name != "go1_rough_asym":
+            cfg, _ = task_registry.get_cfgs(name)
+            assert cfg.env.num_privileged_obs is None and cfg.privileged.terms == (), name
+
+
+def test_header_and_bindings_declare_the_entry_points():
+    from legged_gym_amd.envs.base.privileged import TERMS
+    from legged_gym_amd.sim import abi
+    txt = open(os.path.join(ROOT, "include", "lgx.h")).read()
+    assert re.search(r"int lgx_bind_privileged_obs\(lgx_sim\* sim, float\* buf, const lgx_priv_obs_desc\* desc\);", txt)
+    assert re.search(r"int lgx_rebind_privileged_obs\(lgx_sim\* sim, float\* buf\);", txt)
+    assert {"lgx_bind_privileged_obs", "lgx_rebind_privileged_obs"} <= set(abi.EXPORTED)
+    # enum lgx_priv_term in header order == the ids the layout helper hands to the kernels
+    body = re.search(r"enum lgx_priv_term \{(.*?)\};", re.sub(r"/\*.*?\*/", "", txt, flags=re.S), re.S).group(1)
+    names = [n.strip().split("=")[0].strip() for n in body.split(",") if n.strip()]
+    assert names == ["LGX_PRIV_" + n.upper() for n in ALL_TERMS] + ["LGX_PRIV_COUNT"]
+    assert {n: tid for n, (tid, _) in TERMS.items()} == {n: i for i, n in enumerate(ALL_TERMS)}
+    assert int(re.search(r"#define LGX_MAX_PRIV_OBS (\d+)", txt).group(1)) == abi.MAX_PRIV_OBS == 512
+    assert int(re.search(r"#define LGX_PRIV_MAX_TERMS (\d+)", txt).group(1)) == abi.PRIV_MAX_TERMS
+    assert C.sizeof(abi.LgxPrivObsDesc) == 4 * (2 + 2 * abi.PRIV_MAX_TERMS + 2)
+
+
+def test_bind_validates_a_null_sim_without_a_gpu():
+    """Host-side only: the null-sim check precedes any device call."""
+    import torch  # noqa: F401  (HIP runtime first)
+    from legged_gym_amd.sim import abi
+    lib = abi.declare(C.CDLL(os.path.join(ROOT, "legged_gym_amd", "liblgx.so")))
+    d = abi.LgxPrivObsDesc()
+    d.width = 48
+    assert lib.lgx_bind_privileged_obs(None, C.c_void_p(0x1000), C.byref(d)) == -1
+    assert b"lgx_bind_privileged_obs: null sim" in lib.lgx_last_error()
+    assert lib.lgx_bind_privileged_obs(None, None, None) == -1
+    assert lib.lgx_rebind_privileged_obs(None, C.c_void_p(0x1000)) == -1
+    assert b"lgx_rebind_privileged_obs" in lib.lgx_last_error()
+
+
+def test_oracle_backend_cannot_bind_a_privileged_row():
+    """The CPU oracle mirrors the C structs of the product and has no privileged row: an env that
+    asks for one on it fails at construction instead of training a critic on zeros."""
+    from oracle_backend import make_env
+
+    def asym(cfg):
+        cfg.env.num_privileged_obs = 49
+        cfg.privileged.terms = ("friction",)
+    with pytest.raises(ValueError, match="OracleBackend cannot bind a privileged observation buffer"):
+        make_env("go1_flat_bench", num_envs=4, overrides=asym)
+
+    def mismatch(cfg):
+        cfg.env.num_privileged_obs = 50
+        cfg.privileged.terms = ("friction",)
+    with pytest.raises(ValueError, match="num_privileged_obs = 50"):
+        make_env("go1_flat_bench", num_envs=4, overrides=mismatch)
+
+    def terms_only(cfg):
+        cfg.privileged.terms = ("friction",)
+    with pytest.raises(ValueError, match="num_privileged_obs is None"):
+        make_env("go1_flat_bench", num_envs=4, overrides=terms_only)
+    assert make_env("go1_flat_bench", num_envs=4).privileged_obs_buf is None     # the default: unchanged
+
+
+def hand_env(measure_heights):
+    """Two envs of hand-made state (all values exact in float32)."""
+    t = lambda *rows: torch.tensor(rows, dtype=torch.float32)     # rows -> [len(rows), .]
+    ns = types.SimpleNamespace
+    dof = torch.zeros(2, 12)
+    dof[0, 0], dof[1, 11] = 0.5, -2.0
+    vel = torch.zeros(2, 12)
+    vel[0, 1], vel[1, 2] = 4.0, -3000.0           # -3000 * 0.05 = -150: clipped to -100
+    act = torch.zeros(2, 12)
+    act[0, 3], act[1, 4] = 0.75, -120.0           # clipped to -100
+    cf = torch.zeros(2, 17, 3)
+    cf[0, 4] = t([2.0, -4.0, 50.0])[0]             # foot 0 of env 0: in contact
+    cf[0, 8] = t([0.0, 0.0, 1.0])[0]              # exactly 1.0 is NOT a contact (> 1)
+    cf[1, 16] = t([0.0, 0.0, 20000.0])[0]          # 20000 * 0.01 = 200: clipped to 100
+    tq = torch.zeros(2, 12)
+    tq[0, 0], tq[1, 11] = 10.0, -4000.0           # * 0.05: 0.5, -200 -> -100
+    mass = torch.ones(2, 13)
+    mass[0, 0], mass[1, 0], mass[1, 5] = 1.25, 0.75, 0.5
+    root = torch.zeros(2, 13)
+    root[:, 2] = t([1.0, 3.0])[0]
+    return ns(
+        obs_scales=ns(lin_vel=2.0, ang_vel=0.25, dof_pos=1.0, dof_vel=0.05, height_measurements=5.0),
+        cfg=ns(terrain=ns(measure_heights=measure_heights), normalization=ns(clip_observations=100.0),
+               privileged=ns(terms=ALL_TERMS, contact_force_scale=0.01, torque_scale=0.05)),
+        base_lin_vel=t([1.0, -0.5, 0.25], [0.0, 0.0, 60.0]),        # 60 * 2 = 120: clipped
+        base_ang_vel=t([4.0, 0.0, -8.0], [0.0, 0.0, 0.0]),
+        projected_gravity=t([0.0, 0.0, -1.0], [0.5, 0.0, -0.5]),
+        commands=t([1.0, -1.0, 2.0, 9.0], [0.0, 0.5, 0.0, 9.0]),  # the heading column is not observed
+        commands_scale=t([2.0, 2.0, 0.25])[0],
+        dof_pos=dof, default_dof_pos=torch.full((1, 12), 0.25), dof_vel=vel, actions=act,
+        root_states=root, measured_heights=t([0.25, 0.75], [0.0, 2.5]),
+        contact_forces=cf, torques=tq, friction_coeffs=t([0.5, 1.25])[0], body_mass_scale=mass,
+        feet_indices=torch.tensor([4, 8, 12, 16]))
+
+
+@pytest.mark.parametrize("measure_heights", [False, True])
+def test_reference_row_on_hand_made_tensors(measure_heights):
+    from privileged_obs_ref import privileged_obs_ref
+    row = privileged_obs_ref(hand_env(measure_heights))
+    z = [0.0] * 12
+    e0 = [2.0, -1.0, 0.5, 1.0, 0.0, -2.0, 0.0, 0.0, -1.0, 2.0, -2.0, 0.5]
+    e0 += [0.25] + [-0.25] * 11                              # dof_pos - 0.25
+    e0 += [0.0, 0.2, 0.0] + [0.0] * 9                        # 4 * 0.05 (float32)
+    e0 += [0.0, 0.0, 0.0, 0.75] + [0.0] * 8
+    e1 = [0.0, 0.0, 100.0, 0.0, 0.0, 0.0, 0.5, 0.0, -0.5, 0.0, 1.0, 0.0]
+    e1 += [-0.25] * 11 + [-2.25]
+    e1 += [0.0, 0.0, -100.0] + [0.0] * 9
+    e1 += [0.0, 0.0, 0.0, 0.0, -100.0] + [0.0] * 7
+    if measure_heights:
+        e0 += [1.25, -1.25]      # clip(1 - 0.5 - 0.25, -1, 1) * 5, clip(1 - 0.5 - 0.75, -1, 1) * 5
+        e1 += [5.0, 0.0]         # clip(3 - 0.5 - 0, -1, 1) * 5 = 5, (3 - 0.5 - 2.5) * 5 = 0
+    nobs = 50 if measure_heights else 48
+    assert len(e0) == len(e1) == nobs
+    tail0 = [0.5, 1.25, 1.25] + [1.0] * 12 + [1.0, 0.0, 0.0, 0.0]
+    tail0 += [2.0 * 0.01, -4.0 * 0.01, 50.0 * 0.01] + [0.0, 0.0, 1.0 * 0.01] + z[:6]
+    tail0 += [0.5] + z[:11]
+    tail1 = [1.25, 0.75, 0.75, 1.0, 1.0, 1.0, 1.0, 0.5] + [1.0] * 7 + [0.0, 0.0, 0.0, 1.0]
+    tail1 += z[:9] + [0.0, 0.0, 100.0]
+    tail1 += z[:11] + [-100.0]
+    assert len(tail0) == len(tail1) == 43
+    want = torch.tensor([e0 + tail0, e1 + tail1], dtype=torch.float64).to(torch.float32)
+    # the entries whose product is not exact: rounded once in float32, as numpy does it
+    f = np.float32
+    want[0, 25] = float(f(4.0) * f(0.05))
+    want[0, nobs + 31] = float(f(10.0) * f(0.05))
+    for col, c in ((nobs + 19, 2.0), (nobs + 20, -4.0), (nobs + 21, 50.0), (nobs + 24, 1.0)):
+        want[0, col] = float(f(c) * f(0.01))
+    assert row.shape == (2, nobs + 43) and row.dtype == torch.float32
+    bad = (row != want).nonzero().tolist()
+    assert not bad, [(i, j, row[i, j].item(), want[i, j].item()) for i, j in bad]
