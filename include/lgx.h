@@ -350,6 +350,30 @@ int lgx_bind_privileged_obs(lgx_sim* sim, float* buf, const lgx_priv_obs_desc* d
  * argument or a sim with no row bound. */
 int lgx_rebind_privileged_obs(lgx_sim* sim, float* buf);
 
+/* Observation history for the actor, written by the same launches (no reference counterpart: the
+ * layout is this project's own).  With H = frames and W = frame_width the wide row is
+ *   [ obs (num_obs) | frame_1 (W) | ... | frame_H (W) ],  width = num_obs + H * W floats, rows packed
+ *   obs:     the values the launch writes to the bound obs buffer (noisy, clipped), stored a second time
+ *   frame_k: the first W entries of the obs part of the row this env was given k launches ago - a
+ *            masked copy out of prev_row (frame_1 = prev_row[0, W), frame_k = prev_row's frame k - 1),
+ *            never recomputed or clipped again; 0.0 where that row lies before the episode's first
+ * The mask is a per-env int32 age owned by the sim (allocated and zeroed at bind): at a launch
+ * a = reset[e] (this launch) ? 0 : age[e]; frame k is copied if k <= a, else 0; then
+ * age[e] = min(a + 1, H).  lgx_reset_idx sets age[e] = 0 for its envs and touches no row.
+ * The bound obs buffer, its stride and LGX_BUF_OBS are unchanged. */
+typedef struct lgx_obs_history_desc { int32_t frames, frame_width, width; } lgx_obs_history_desc;
+/* Bind the wide row output and the row of the previous launch (device float[N, desc->width] each;
+ * the kernel never works in place) for the next calls.  row == NULL unbinds and frees the age array
+ * (the other arguments are then ignored and the launches are the ones of a sim that never bound a
+ * history).  LGX_EINVAL (message in lgx_last_error) for a null sim, prev_row or desc,
+ * row == prev_row, frames < 1, a frame_width outside [1, num_obs], width != num_obs + frames *
+ * frame_width, or width > LGX_MAX_PRIV_OBS. */
+int lgx_bind_obs_history(lgx_sim* sim, float* row, const float* prev_row, const lgx_obs_history_desc* desc);
+/* Re-point the two rows, layout and ages unchanged (callers alternate two buffers: this launch's
+ * row is the next launch's prev_row).  LGX_EINVAL for a null argument, row == prev_row, or a sim
+ * with no history bound. */
+int lgx_rebind_obs_history(lgx_sim* sim, float* row, const float* prev_row);
+
 /* Data-parallel gradient all-reduce over RCCL (SURVEY §8(b) lgx_allreduce_grads; §8(e): the
  * gradient average of a multi-GPU PPO update, one rank per GPU).  One communicator per rank,
  * created collectively from a unique id that rank 0 draws and the caller distributes (e.g. over

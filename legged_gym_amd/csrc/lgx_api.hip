@@ -44,6 +44,7 @@ struct lgx_sim {
   const float* draws;
   float* extras_snapshot;  // lgx_rebind_extras (NULL: no per-call copy)
   lgx_priv_args priv;      // lgx_bind_privileged_obs (buf NULL: no privileged row)
+  lgx_hist_args hist;      // lgx_bind_obs_history (row NULL: no history; age is owned here)
   // Go1 actuator net off the critical path: its output (dVel) is not read by the step
   // (go1.py:71-73), so it runs on an auxiliary stream concurrently with post-physics and the
   // next policy forward; the next physics launch (which rewrites model_ins) waits for it.
@@ -204,6 +205,7 @@ int lgx_sim_create(const lgx_model* model, const lgx_env_params* params, const l
   s->draws = nullptr;
   s->extras_snapshot = nullptr;
   s->priv = lgx_priv_args{};
+  s->hist = lgx_hist_args{};
   s->aux = nullptr;
   s->aux_in = s->aux_done = nullptr;
   s->aux_pending = false;
@@ -236,6 +238,7 @@ int lgx_sim_destroy(lgx_sim* s) {
   }
   for (auto& v : s->ev) for (hipEvent_t e : v) (void)hipEventDestroy(e);
   for (hipEvent_t e : s->pool) (void)hipEventDestroy(e);
+  (void)hipFree(s->hist.age);
   (void)hipFree(s->d_model);
   (void)hipFree(s->d_params);
   delete s;
@@ -354,6 +357,46 @@ int lgx_rebind_privileged_obs(lgx_sim* s, float* buf) {
   return 0;
 }
 
+int lgx_bind_obs_history(lgx_sim* s, float* row, const float* prev, const lgx_obs_history_desc* d) {
+  if (!s) return fail(LGX_EINVAL, "lgx_bind_obs_history: null sim");
+  if (!row) {
+    int rc = s->hist.age ? hip_check(hipFree(s->hist.age), "lgx_bind_obs_history: hipFree(age)") : 0;
+    s->hist = lgx_hist_args{};
+    return rc;
+  }
+  if (!prev) return fail(LGX_EINVAL, "lgx_bind_obs_history: null prev_row");
+  if (!d) return fail(LGX_EINVAL, "lgx_bind_obs_history: null desc");
+  if (row == prev) return fail(LGX_EINVAL, "lgx_bind_obs_history: row and prev_row are the same buffer");
+  const lgx_env_params& p = s->params;
+  if (d->frames < 1) return fail(LGX_EINVAL, "lgx_bind_obs_history: frames is below 1");
+  if (d->frame_width < 1 || d->frame_width > p.num_obs)
+    return fail(LGX_EINVAL, "lgx_bind_obs_history: frame_width is outside [1, num_obs]");
+  if ((int64_t)d->width != (int64_t)p.num_obs + (int64_t)d->frames * d->frame_width)
+    return fail(LGX_EINVAL, "lgx_bind_obs_history: width is not num_obs + frames * frame_width");
+  if (d->width > LGX_MAX_PRIV_OBS) return fail(LGX_EINVAL, "lgx_bind_obs_history: width is above LGX_MAX_PRIV_OBS");
+  // a (re)bind starts every env without a past: allocate once, zero every time.  A setup call: the
+  // device is drained before and after the memset, so it is ordered against launches on any stream
+  int32_t* age = s->hist.age;
+  if (!age) {
+    if (int rc = hip_check(hipMalloc(&age, sizeof(int32_t) * (size_t)p.num_envs), "lgx_bind_obs_history: hipMalloc(age)"))
+      return rc;
+  }
+  s->hist = lgx_hist_args{row, prev, age, d->frames, d->frame_width, d->width};
+  if (int rc = hip_check(hipDeviceSynchronize(), "lgx_bind_obs_history: hipDeviceSynchronize")) return rc;
+  if (int rc = hip_check(hipMemset(age, 0, sizeof(int32_t) * (size_t)p.num_envs), "lgx_bind_obs_history: hipMemset(age)"))
+    return rc;
+  return hip_check(hipDeviceSynchronize(), "lgx_bind_obs_history: hipDeviceSynchronize");
+}
+
+int lgx_rebind_obs_history(lgx_sim* s, float* row, const float* prev) {
+  if (!s || !row || !prev) return fail(LGX_EINVAL, "lgx_rebind_obs_history: null argument");
+  if (!s->hist.row) return fail(LGX_EINVAL, "lgx_rebind_obs_history: no observation history is bound");
+  if (row == prev) return fail(LGX_EINVAL, "lgx_rebind_obs_history: row and prev_row are the same buffer");
+  s->hist.row = row;
+  s->hist.prev = prev;
+  return 0;
+}
+
 int lgx_rebind_extras(lgx_sim* s, float* snapshot) {
   if (!s) return fail(LGX_EINVAL, "lgx_rebind_extras: null sim");
   s->extras_snapshot = snapshot;
@@ -403,7 +446,7 @@ int lgx_post_physics(lgx_sim* s, int64_t step, void* stream) {
   if (!s) return fail(LGX_EINVAL, "lgx_post_physics: null sim");
   return launch_check(lgx_launch_post_physics(s->d_params, s->bufs, s->params.num_envs, s->params.num_obs, s->n_term_rows,
                                               s->params.measure_heights, step, s->draws, s->extras_snapshot, s->priv,
-                                              (hipStream_t)stream),
+                                              s->hist, (hipStream_t)stream),
                       "lgx_post_physics: launch");
 }
 
@@ -440,7 +483,7 @@ static int post_physics_fused(lgx_sim* s, int64_t step, hipStream_t st, bool sam
     rc = launch_check(lgx_launch_post_physics_act(s->d_params, s->bufs, p.num_envs, step, s->draws, s->extras_snapshot,
                                                   s->bufs.model_ins, s->bufs.act_dvel,
                                                   (int64_t)p.decimation * p.num_envs * 4, s->bufs.act_net_w,
-                                                  s->bufs.act_net_scale, s->priv, st),
+                                                  s->bufs.act_net_scale, s->priv, s->hist, st),
                       "lgx_step: post-physics + actuator launch");
     lgx_timing = lgx_timing_slot{};
     return rc;
@@ -516,7 +559,7 @@ int lgx_reset_idx(lgx_sim* s, const int32_t* env_ids, int32_t n, int64_t step, i
   if (!s || n < 0 || (n > 0 && !env_ids)) return fail(LGX_EINVAL, "lgx_reset_idx: bad arguments");
   if (n > s->params.num_envs) return fail(LGX_EINVAL, "lgx_reset_idx: more ids than envs");
   return launch_check(lgx_launch_reset_idx(s->d_params, s->bufs, s->params.num_envs, s->n_term_rows, env_ids, n, step,
-                                           init_done, s->draws, s->extras_snapshot, (hipStream_t)stream),
+                                           init_done, s->draws, s->extras_snapshot, s->hist.age, (hipStream_t)stream),
                       "lgx_reset_idx: launch");
 }
 

@@ -327,13 +327,39 @@ LGX_DEV void priv_tail(const lgx_env_params* __restrict__ P, const lgx_buffers& 
   }
 }
 
+// each env's history age a of this launch, staged by its lane in phase B for the lanes of hist_tail
+LGX_DEV int* hist_age_lds() {
+  __shared__ int sage[LGX_ENV_BLOCK];
+  return sage;
+}
+
+// the history tail of the wide rows of one workgroup's envs (lgx.h, lgx_bind_obs_history): a masked
+// copy out of the previous launch's rows, one float per lane, consecutive lanes on consecutive
+// columns of both rows (rows are `width` floats apart and the tail starts at column nobs: no
+// alignment to assume).  Tail column c belongs to frame c / W + 1 and comes from column c of the
+// previous row's obs part (frame 1) or from its tail column c - W (frame k from frame k - 1).
+// sage: each env's staged age a (phase B); the load is unconditional (prev is a whole row buffer),
+// the mask selects.
+LGX_DEV void hist_tail(const lgx_hist_args& hv, const int* sage, int nobs, int N, int e0) {
+  const int W = hv.frame_width, tw = hv.frames * W;
+  for (int idx = threadIdx.x; idx < LGX_ENV_BLOCK * tw; idx += ENV_THREADS) {
+    const int le = idx / tw, c = idx - le * tw;
+    const int e = e0 + le;
+    if (e >= N) break;
+    const int64_t r = (int64_t)e * hv.width;
+    const float v = hv.prev[r + (c < W ? c : nobs + c - W)];
+    hv.row[r + nobs + c] = c < sage[le] * W ? v : 0.f;   // frame k = c / W + 1 <= a
+  }
+}
+
 // one post-physics workgroup: envs [blk * LGX_ENV_BLOCK, +LGX_ENV_BLOCK) of nblocks.  PRIV: also
-// the privileged rows (pv; lgx_bind_privileged_obs) - compiled apart, so that the instantiation a
-// sim without a bound row launches carries none of it
-template <bool PRIV>
+// the privileged rows (pv; lgx_bind_privileged_obs); HIST: also the wide rows with the observation
+// history (hv; lgx_bind_obs_history) - compiled apart, so that the instantiation a sim with
+// neither bound launches carries none of it
+template <bool PRIV, bool HIST>
 LGX_DEV void post_physics_body(const lgx_env_params* __restrict__ P, const lgx_buffers& B, int64_t step,
                                const float* draws, int blk, int nblocks, float* snapshot,
-                               const lgx_priv_args& pv) {
+                               const lgx_priv_args& pv, const lgx_hist_args& hv) {
   const int N = P->num_envs;
   const int nobs = P->num_obs;
   const int e0 = blk * LGX_ENV_BLOCK;
@@ -561,6 +587,7 @@ LGX_DEV void post_physics_body(const lgx_env_params* __restrict__ P, const lgx_b
 #pragma unroll
       for (int k = 0; k < 4; ++k) sbase[tid][9 + k] = v.cmd[k];
       sbase[tid][13] = v.reset ? rs[2] : rs0[2];   // post-reset root z
+      if constexpr (HIST) hist_age_lds()[tid] = v.reset ? 0 : hv.age[e];   // a: an episode that starts here has no past
       for (int k = 0; k < 4; ++k) cmd_g[k] = v.cmd[k];
       if (P->curriculum) part[tid][T + 1] = (float)B.terrain_levels[e];
       float* o3 = B.base_lin_vel + (int64_t)e * 3;
@@ -615,6 +642,7 @@ LGX_DEV void post_physics_body(const lgx_env_params* __restrict__ P, const lgx_b
         pv.buf[(int64_t)e * pv.width + i] = clampf(priv_clean(v - obs_sub[i], obs_mul[i]), -clip, clip);
       if (noise) o += (2.f * nz[u] - 1.f) * obs_nsc[i];
       B.obs[(int64_t)e * nobs + i] = clampf(o, -clip, clip);
+      if constexpr (HIST) hv.row[(int64_t)e * hv.width + i] = clampf(o, -clip, clip);   // the same value again
     }
   }
   const int nqh = nq - nq0;   // height quads
@@ -636,9 +664,16 @@ LGX_DEV void post_physics_body(const lgx_env_params* __restrict__ P, const lgx_b
         pv.buf[(int64_t)e * pv.width + i] = clampf(priv_clean(v - obs_sub[i], obs_mul[i]), -clip, clip);
       if (noise) o += (2.f * nz[u] - 1.f) * obs_nsc[i];
       B.obs[(int64_t)e * nobs + i] = clampf(o, -clip, clip);
+      if constexpr (HIST) hv.row[(int64_t)e * hv.width + i] = clampf(o, -clip, clip);   // the same value again
     }
   }
   if constexpr (PRIV) priv_tail(P, B, pv, srow, e0);
+  if constexpr (HIST) {
+    // sage was written in phase B, barriers ago; age[e] is read and written by env e's lane alone
+    const int* sage = hist_age_lds();
+    hist_tail(hv, sage, nobs, N, e0);
+    if (tid < LGX_ENV_BLOCK && e0 + tid < N) hv.age[e0 + tid] = min(sage[tid] + 1, hv.frames);
+  }
   LGX_CLK(4);
   // ---- last_* copies (:136-138), post-reset values
   for (int idx = tid; idx < LGX_ENV_BLOCK * 12; idx += ENV_THREADS) {
@@ -659,19 +694,35 @@ LGX_DEV void post_physics_body(const lgx_env_params* __restrict__ P, const lgx_b
   }
 }
 
+// one persistent actuator workgroup per CU next to the post-physics workgroups
+int actuator_workgroups(int64_t act_rows) {
+  const int64_t tiles = (act_rows + WS_BM - 1) / WS_BM;
+  int dev = 0, cus = 256;
+  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+  return (int)std::max<int64_t>(1, std::min<int64_t>(tiles, cus));
+}
+
 }  // namespace
+
+// This file is compiled twice.  On its own it gives the kernels of a sim without an observation
+// history; lgx_envlogic_hist.hip includes it with LGX_ENVLOGIC_HIST defined and gives the history
+// instantiations and their launchers, nothing else.  They are kept out of this translation unit
+// because instantiations compiled together perturb each other's code generation (with them here the
+// privileged kernels came out with the operands of one integer add swapped), and the kernels
+// launched with no history bound are meant to stay the machine code they were (tools/kernel_code_diff.py).
+#ifndef LGX_ENVLOGIC_HIST
 
 __global__ void __launch_bounds__(ENV_THREADS)
 lgx_post_physics_kernel(const lgx_env_params* __restrict__ P, lgx_buffers B, int64_t step, const float* draws,
                         float* snapshot) {
-  post_physics_body<false>(P, B, step, draws, blockIdx.x, gridDim.x, snapshot, lgx_priv_args{});
+  post_physics_body<false, false>(P, B, step, draws, blockIdx.x, gridDim.x, snapshot, lgx_priv_args{}, lgx_hist_args{});
 }
 
 // the same with a privileged row bound
 __global__ void __launch_bounds__(ENV_THREADS)
 lgx_post_physics_priv_kernel(const lgx_env_params* __restrict__ P, lgx_buffers B, int64_t step, const float* draws,
                              float* snapshot, lgx_priv_args pv) {
-  post_physics_body<true>(P, B, step, draws, blockIdx.x, gridDim.x, snapshot, pv);
+  post_physics_body<true, false>(P, B, step, draws, blockIdx.x, gridDim.x, snapshot, pv, lgx_hist_args{});
 }
 
 // post-physics and the Go1 actuator network in ONE launch: workgroups [0, nblocks) are the
@@ -683,7 +734,7 @@ __global__ void __launch_bounds__(ENV_THREADS, 2)
 lgx_post_physics_act_kernel(const lgx_env_params* __restrict__ P, lgx_buffers B, int64_t step, const float* draws,
                             float* snapshot, WsArgs wa, int32_t nblocks) {
   if ((int)blockIdx.x < nblocks)
-    post_physics_body<false>(P, B, step, draws, blockIdx.x, nblocks, snapshot, lgx_priv_args{});
+    post_physics_body<false, false>(P, B, step, draws, blockIdx.x, nblocks, snapshot, lgx_priv_args{}, lgx_hist_args{});
   else actuator_ws_body(wa, blockIdx.x - nblocks, gridDim.x - nblocks);
 }
 
@@ -691,14 +742,15 @@ lgx_post_physics_act_kernel(const lgx_env_params* __restrict__ P, lgx_buffers B,
 __global__ void __launch_bounds__(ENV_THREADS, 2)
 lgx_post_physics_act_priv_kernel(const lgx_env_params* __restrict__ P, lgx_buffers B, int64_t step, const float* draws,
                                  float* snapshot, WsArgs wa, int32_t nblocks, lgx_priv_args pv) {
-  if ((int)blockIdx.x < nblocks) post_physics_body<true>(P, B, step, draws, blockIdx.x, nblocks, snapshot, pv);
+  if ((int)blockIdx.x < nblocks)
+    post_physics_body<true, false>(P, B, step, draws, blockIdx.x, nblocks, snapshot, pv, lgx_hist_args{});
   else actuator_ws_body(wa, blockIdx.x - nblocks, gridDim.x - nblocks);
 }
 
 // reset_idx on an explicit env list (BaseTask.reset, base_task.py:111-115)
 __global__ void __launch_bounds__(LGX_ENV_BLOCK)
 lgx_reset_idx_kernel(const lgx_env_params* __restrict__ P, lgx_buffers B, const int32_t* ids, int32_t n, int64_t step,
-                     int32_t init_done, const float* draws) {
+                     int32_t init_done, const float* draws, int32_t* hist_age) {
   const int N = P->num_envs;
   const int T = P->num_terms + (P->termination_slot >= 0 ? 1 : 0);
   const Draws D{P, draws, LGX_DRAW_NOISE + P->num_obs};
@@ -716,6 +768,7 @@ lgx_reset_idx_kernel(const lgx_env_params* __restrict__ P, lgx_buffers B, const 
     }
     part[tid][T] = 1.f;
     reset_env(P, B, D, e, step, 1u, init_done != 0, cmd);
+    if (hist_age) hist_age[e] = 0;   // the episode starts here: its next row has no past (lgx_bind_obs_history)
     for (int c = 0; c < 4; ++c) B.commands[(int64_t)e * 4 + c] = cmd[c];
   }
   block_partials(part, T, B.scratch + (int64_t)blockIdx.x * LGX_PARTIAL_STRIDE);
@@ -729,8 +782,10 @@ lgx_extras_finalize_kernel(const lgx_env_params* __restrict__ P, lgx_buffers B, 
 
 int lgx_launch_post_physics(const lgx_env_params* dp, const lgx_buffers& b, int32_t n_envs, int32_t num_obs,
                             int32_t n_term_rows, int32_t measure_heights, int64_t step, const float* draws,
-                            float* extras_snapshot, const lgx_priv_args& pv, hipStream_t stream) {
+                            float* extras_snapshot, const lgx_priv_args& pv, const lgx_hist_args& hv,
+                            hipStream_t stream) {
   (void)num_obs; (void)n_term_rows; (void)measure_heights;
+  if (hv.row) return lgx_launch_post_physics_hist(dp, b, n_envs, step, draws, extras_snapshot, pv, hv, stream);
   int blocks = (n_envs + LGX_ENV_BLOCK - 1) / LGX_ENV_BLOCK;
   if (pv.buf)
     LGX_LAUNCH(lgx_post_physics_priv_kernel, dim3(blocks), dim3(ENV_THREADS), 0, stream, dp, b, step, draws,
@@ -744,14 +799,13 @@ int lgx_launch_post_physics(const lgx_env_params* dp, const lgx_buffers& b, int3
 int lgx_launch_post_physics_act(const lgx_env_params* dp, const lgx_buffers& b, int32_t n_envs, int64_t step,
                                 const float* draws, float* extras_snapshot, const float* act_in, float* act_out,
                                 int64_t act_rows, const float* act_w, const float* act_scale,
-                                const lgx_priv_args& pv, hipStream_t stream) {
+                                const lgx_priv_args& pv, const lgx_hist_args& hv, hipStream_t stream) {
   static_assert(ENV_THREADS == 256, "the actuator-net workgroups are 256 threads");
+  if (hv.row)
+    return lgx_launch_post_physics_act_hist(dp, b, n_envs, step, draws, extras_snapshot, act_in, act_out, act_rows,
+                                            act_w, act_scale, pv, hv, stream);
   const int blocks = (n_envs + LGX_ENV_BLOCK - 1) / LGX_ENV_BLOCK;
-  const int64_t tiles = (act_rows + WS_BM - 1) / WS_BM;
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  // one persistent actuator workgroup per CU next to the post-physics workgroups
-  const int act_wgs = (int)std::max<int64_t>(1, std::min<int64_t>(tiles, cus));
+  const int act_wgs = actuator_workgroups(act_rows);
   WsArgs wa{act_in, act_out, act_rows, act_w, act_scale};
   if (pv.buf)
     LGX_LAUNCH(lgx_post_physics_act_priv_kernel, dim3(blocks + act_wgs), dim3(ENV_THREADS), 0, stream, dp, b, step,
@@ -764,12 +818,74 @@ int lgx_launch_post_physics_act(const lgx_env_params* dp, const lgx_buffers& b, 
 
 int lgx_launch_reset_idx(const lgx_env_params* dp, const lgx_buffers& b, int32_t n_envs, int32_t n_term_rows,
                          const int32_t* ids, int32_t n, int64_t step, int32_t init_done, const float* draws,
-                         float* extras_snapshot, hipStream_t stream) {
+                         float* extras_snapshot, int32_t* hist_age, hipStream_t stream) {
   (void)n_envs; (void)n_term_rows;
   if (n <= 0) return 0;
   int blocks = (n + LGX_ENV_BLOCK - 1) / LGX_ENV_BLOCK;
   hipLaunchKernelGGL(lgx_reset_idx_kernel, dim3(blocks), dim3(LGX_ENV_BLOCK), 0, stream, dp, b, ids, n, step,
-                     init_done, draws);
+                     init_done, draws, hist_age);
   hipLaunchKernelGGL(lgx_extras_finalize_kernel, dim3(1), dim3(256), 0, stream, dp, b, blocks, 1, extras_snapshot);
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
+
+#else  // LGX_ENVLOGIC_HIST: the instantiations with an observation history bound, without and with a privileged row
+
+__global__ void __launch_bounds__(ENV_THREADS)
+lgx_post_physics_hist_kernel(const lgx_env_params* __restrict__ P, lgx_buffers B, int64_t step, const float* draws,
+                             float* snapshot, lgx_hist_args hv) {
+  post_physics_body<false, true>(P, B, step, draws, blockIdx.x, gridDim.x, snapshot, lgx_priv_args{}, hv);
+}
+
+__global__ void __launch_bounds__(ENV_THREADS)
+lgx_post_physics_priv_hist_kernel(const lgx_env_params* __restrict__ P, lgx_buffers B, int64_t step,
+                                  const float* draws, float* snapshot, lgx_priv_args pv, lgx_hist_args hv) {
+  post_physics_body<true, true>(P, B, step, draws, blockIdx.x, gridDim.x, snapshot, pv, hv);
+}
+
+// with the Go1 actuator-net workgroups in the launch (still two workgroups per CU)
+__global__ void __launch_bounds__(ENV_THREADS, 2)
+lgx_post_physics_act_hist_kernel(const lgx_env_params* __restrict__ P, lgx_buffers B, int64_t step, const float* draws,
+                                 float* snapshot, WsArgs wa, int32_t nblocks, lgx_hist_args hv) {
+  if ((int)blockIdx.x < nblocks)
+    post_physics_body<false, true>(P, B, step, draws, blockIdx.x, nblocks, snapshot, lgx_priv_args{}, hv);
+  else actuator_ws_body(wa, blockIdx.x - nblocks, gridDim.x - nblocks);
+}
+
+__global__ void __launch_bounds__(ENV_THREADS, 2)
+lgx_post_physics_act_priv_hist_kernel(const lgx_env_params* __restrict__ P, lgx_buffers B, int64_t step,
+                                      const float* draws, float* snapshot, WsArgs wa, int32_t nblocks,
+                                      lgx_priv_args pv, lgx_hist_args hv) {
+  if ((int)blockIdx.x < nblocks) post_physics_body<true, true>(P, B, step, draws, blockIdx.x, nblocks, snapshot, pv, hv);
+  else actuator_ws_body(wa, blockIdx.x - nblocks, gridDim.x - nblocks);
+}
+
+int lgx_launch_post_physics_hist(const lgx_env_params* dp, const lgx_buffers& b, int32_t n_envs, int64_t step,
+                                 const float* draws, float* extras_snapshot, const lgx_priv_args& pv,
+                                 const lgx_hist_args& hv, hipStream_t stream) {
+  int blocks = (n_envs + LGX_ENV_BLOCK - 1) / LGX_ENV_BLOCK;
+  if (pv.buf)
+    LGX_LAUNCH(lgx_post_physics_priv_hist_kernel, dim3(blocks), dim3(ENV_THREADS), 0, stream, dp, b, step, draws,
+               extras_snapshot, pv, hv);
+  else
+    LGX_LAUNCH(lgx_post_physics_hist_kernel, dim3(blocks), dim3(ENV_THREADS), 0, stream, dp, b, step, draws,
+               extras_snapshot, hv);
+  return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+int lgx_launch_post_physics_act_hist(const lgx_env_params* dp, const lgx_buffers& b, int32_t n_envs, int64_t step,
+                                     const float* draws, float* extras_snapshot, const float* act_in, float* act_out,
+                                     int64_t act_rows, const float* act_w, const float* act_scale,
+                                     const lgx_priv_args& pv, const lgx_hist_args& hv, hipStream_t stream) {
+  const int blocks = (n_envs + LGX_ENV_BLOCK - 1) / LGX_ENV_BLOCK;
+  const int act_wgs = actuator_workgroups(act_rows);
+  WsArgs wa{act_in, act_out, act_rows, act_w, act_scale};
+  if (pv.buf)
+    LGX_LAUNCH(lgx_post_physics_act_priv_hist_kernel, dim3(blocks + act_wgs), dim3(ENV_THREADS), 0, stream, dp, b,
+               step, draws, extras_snapshot, wa, blocks, pv, hv);
+  else
+    LGX_LAUNCH(lgx_post_physics_act_hist_kernel, dim3(blocks + act_wgs), dim3(ENV_THREADS), 0, stream, dp, b, step,
+               draws, extras_snapshot, wa, blocks, hv);
+  return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+#endif  // LGX_ENVLOGIC_HIST

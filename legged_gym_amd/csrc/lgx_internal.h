@@ -49,19 +49,37 @@ struct lgx_priv_args {
   }
 };
 static_assert(LGX_PRIV_MAX_TERMS <= 8 && LGX_PRIV_COUNT <= 16 && LGX_MAX_PRIV_OBS < 65536, "lgx_priv_args packing");
-// pv.buf == nullptr launches the kernels of a sim without a privileged row (no other kernel argument
-// or code); otherwise their privileged instantiations
+// the observation history of a sim (lgx_bind_obs_history, checked there), passed by value to the
+// post-physics launches; row == nullptr: nothing bound.  age: the sim's int32[N] (lgx.h)
+struct lgx_hist_args {
+  float* row;            // [N, width]: this launch's output
+  const float* prev;     // [N, width]: the previous launch's row, != row
+  int32_t* age;
+  int32_t frames, frame_width, width;
+};
+// pv.buf == nullptr and hv.row == nullptr launch the kernels of a sim with neither bound (no other
+// kernel argument or code); otherwise the instantiation with the privileged row, the history or both
 int lgx_launch_post_physics(const lgx_env_params* dp, const lgx_buffers& b, int32_t n_envs, int32_t num_obs,
                             int32_t n_term_rows, int32_t measure_heights, int64_t step, const float* draws,
-                            float* extras_snapshot, const lgx_priv_args& pv, hipStream_t stream);
+                            float* extras_snapshot, const lgx_priv_args& pv, const lgx_hist_args& hv,
+                            hipStream_t stream);
 // post-physics + the Go1 actuator net (act_rows rows of act_in -> act_out) in one launch
 int lgx_launch_post_physics_act(const lgx_env_params* dp, const lgx_buffers& b, int32_t n_envs, int64_t step,
                                 const float* draws, float* extras_snapshot, const float* act_in, float* act_out,
                                 int64_t act_rows, const float* act_w, const float* act_scale,
-                                const lgx_priv_args& pv, hipStream_t stream);
+                                const lgx_priv_args& pv, const lgx_hist_args& hv, hipStream_t stream);
+// the same two launches with a history bound (hv.row != nullptr; lgx_envlogic_hist.hip), to which the two above forward
+int lgx_launch_post_physics_hist(const lgx_env_params* dp, const lgx_buffers& b, int32_t n_envs, int64_t step,
+                                 const float* draws, float* extras_snapshot, const lgx_priv_args& pv,
+                                 const lgx_hist_args& hv, hipStream_t stream);
+int lgx_launch_post_physics_act_hist(const lgx_env_params* dp, const lgx_buffers& b, int32_t n_envs, int64_t step,
+                                     const float* draws, float* extras_snapshot, const float* act_in, float* act_out,
+                                     int64_t act_rows, const float* act_w, const float* act_scale,
+                                     const lgx_priv_args& pv, const lgx_hist_args& hv, hipStream_t stream);
+// hist_age: the bound history's ages (zeroed for the listed envs) or nullptr
 int lgx_launch_reset_idx(const lgx_env_params* dp, const lgx_buffers& b, int32_t n_envs, int32_t n_term_rows,
                          const int32_t* ids, int32_t n, int64_t step, int32_t init_done, const float* draws,
-                         float* extras_snapshot, hipStream_t stream);
+                         float* extras_snapshot, int32_t* hist_age, hipStream_t stream);
 // wg_per_cu: persistent workgroups per CU of the weight-stationary kernel (2 when it owns the
 // chip, 1 when it shares the CUs with concurrent work on another stream)
 int lgx_launch_actuator_mlp(const float* in, float* out, int64_t rows, const float* w, const float* out_scale,

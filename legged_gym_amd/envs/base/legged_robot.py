@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from legged_gym_amd import LEGGED_GYM_ROOT_DIR
-from legged_gym_amd.envs.base import privileged
+from legged_gym_amd.envs.base import history, privileged
 from legged_gym_amd.envs.base.base_task import BaseTask
 from legged_gym_amd.sim import abi
 from legged_gym_amd.sim.model import RobotAsset, build_model, resolve_asset_path
@@ -96,6 +96,20 @@ class LgxBackend:
         self._check(self.lib.lgx_rebind_privileged_obs(self.handle, C.c_void_p(buf.data_ptr())),
                     "lgx_rebind_privileged_obs")
 
+    def bind_obs_history(self, row, prev_row, layout):
+        """lgx_bind_obs_history: the wide row output, the previous step's row and the layout
+        (envs/base/history.py); row None unbinds."""
+        if row is None:
+            self._check(self.lib.lgx_bind_obs_history(self.handle, None, None, None), "lgx_bind_obs_history")
+            return
+        d = abi.LgxObsHistoryDesc(layout.frames, layout.frame_width, layout.width)
+        self._check(self.lib.lgx_bind_obs_history(self.handle, C.c_void_p(row.data_ptr()),
+                                                  C.c_void_p(prev_row.data_ptr()), C.byref(d)), "lgx_bind_obs_history")
+
+    def rebind_obs_history(self, row, prev_row):
+        self._check(self.lib.lgx_rebind_obs_history(self.handle, C.c_void_p(row.data_ptr()),
+                                                    C.c_void_p(prev_row.data_ptr())), "lgx_rebind_obs_history")
+
     def sync_aux(self):
         self._check(self.lib.lgx_sync_aux(self.handle, self.stream()), "lgx_sync_aux")
 
@@ -139,6 +153,9 @@ class LeggedRobot(BaseTask):
         self.height_samples = None
         self.debug_viz = False
         self.init_done = False
+        # the kernel's observation row (lgx_env_params.num_obs, the noise vector, the clean part of a
+        # privileged row); num_obs, the VecEnv attribute, is wider with cfg.history (_bind_obs_history)
+        self.num_base_obs = cfg.env.num_observations
         self._parse_cfg(self.cfg)
         super().__init__(self.cfg, sim_params, physics_engine, sim_device, headless)
         self._init_buffers()
@@ -194,7 +211,11 @@ class LeggedRobot(BaseTask):
         self._lgx_bufs.obs = _ptr(ob)
         if hasattr(self._backend, "rebind_obs"):
             self._backend.rebind_obs(ob)
-        self.obs_buf = ob
+        if self._hist_bufs is None:
+            self.obs_buf = ob
+        else:   # the wide row is what the env returns; the slot it returned last is this step's prev_row
+            self.obs_buf = self._hist_bufs[self._obs_slot]
+            self._backend.rebind_obs_history(self.obs_buf, self._hist_bufs[self._obs_slot ^ 1])
         if self._priv_bufs is not None:    # the critic's row likewise: storage copies it after env.step
             pb = self._priv_bufs[self._obs_slot]
             self._backend.rebind_privileged_obs(pb)
@@ -413,7 +434,7 @@ class LeggedRobot(BaseTask):
         self.default_dof_pos = self.default_dof_pos.unsqueeze(0)
 
     def _get_noise_scale_vec(self, cfg):  # legged_robot.py:477-500
-        nv = torch.zeros_like(self.obs_buf[0])
+        nv = torch.zeros(self.num_base_obs, dtype=torch.float, device=self.device)
         self.add_noise = self.cfg.noise.add_noise
         ns, nl, os_ = self.cfg.noise.noise_scales, self.cfg.noise.noise_level, self.obs_scales
         nv[:3] = ns.lin_vel * nl * os_.lin_vel
@@ -481,7 +502,7 @@ class LeggedRobot(BaseTask):
         cfg, N = self.cfg, self.num_envs
         self._lgx_model = build_model(self.asset, cfg, self.sim_params)
         p = abi.LgxEnvParams()
-        p.num_envs, p.num_obs, p.decimation = N, self.num_obs, cfg.control.decimation
+        p.num_envs, p.num_obs, p.decimation = N, self.num_base_obs, cfg.control.decimation
         p.control_type = self._control_type()
         p.action_scale = cfg.control.action_scale
         p.clip_actions = cfg.normalization.clip_actions
@@ -511,7 +532,7 @@ class LeggedRobot(BaseTask):
         p.obs_scale_dof_pos, p.obs_scale_dof_vel, p.obs_scale_height = os_.dof_pos, os_.dof_vel, os_.height_measurements
         p.add_noise = int(bool(self.add_noise))
         nv = self.noise_scale_vec.cpu().numpy()
-        for i in range(self.num_obs):
+        for i in range(self.num_base_obs):
             p.noise_scale_vec[i] = nv[i]
         p.terrain_kind = 1 if self.height_samples is not None else 0
         p.measure_heights = int(bool(cfg.terrain.measure_heights))
@@ -584,8 +605,10 @@ class LeggedRobot(BaseTask):
         self._obs_bufs = [self.obs_buf, torch.zeros_like(self.obs_buf)]
         self._obs_slot = 0
         layout = self._privileged_layout()
+        hist_layout = self._history_layout()
         self._backend = self._make_backend(self._lgx_model, p, b)
         self._bind_privileged_obs(layout)
+        self._bind_obs_history(hist_layout)
 
     def _privileged_layout(self):
         """The critic's row `[clean obs | cfg.privileged.terms]` (envs/base/privileged.py), or None
@@ -597,7 +620,7 @@ class LeggedRobot(BaseTask):
                 raise ValueError(f"privileged.terms = {terms} but env.num_privileged_obs is None: set it to "
                                  "num_observations + the terms' width")
             return None
-        return privileged.layout(terms, self.num_obs, len(self.feet_indices), self.num_privileged_obs)
+        return privileged.layout(terms, self.num_base_obs, len(self.feet_indices), self.num_privileged_obs)
 
     def _bind_privileged_obs(self, layout):
         """Bind the two alternating privileged rows to the kernels (lgx_bind_privileged_obs)."""
@@ -613,6 +636,29 @@ class LeggedRobot(BaseTask):
         self._backend.bind_privileged_obs(self._priv_bufs[self._obs_slot], layout,
                                           float(getattr(pcfg, "contact_force_scale", 0.01)),
                                           float(getattr(pcfg, "torque_scale", 0.05)))
+
+    def _history_layout(self):
+        """The actor's row `[obs | cfg.history.frames frames]` (envs/base/history.py), or None
+        without a history; ValueError for a config that does not add up."""
+        hcfg = getattr(self.cfg, "history", None)
+        return history.layout(getattr(hcfg, "frames", 0), getattr(hcfg, "frame_width", 48), self.num_base_obs)
+
+    def _bind_obs_history(self, layout):
+        """Make the wide row the env's observation (obs_buf, num_obs) and bind its two alternating
+        buffers to the kernels (lgx_bind_obs_history).  The kernel's own row (lgx_buffers.obs,
+        num_base_obs wide) keeps alternating in _obs_bufs."""
+        self.history_layout, self._hist_bufs = layout, None
+        if layout is None:
+            return
+        if not hasattr(self._backend, "bind_obs_history"):
+            raise ValueError(f"history.frames = {layout.frames}: the backend {type(self._backend).__name__} cannot "
+                             "bind an observation history (the CPU oracle backend of the tests has none; the lgx "
+                             "backend writes it)")
+        self._hist_bufs = [torch.zeros(self.num_envs, layout.width, dtype=torch.float, device=self.device)
+                           for _ in range(2)]
+        self._backend.bind_obs_history(self._hist_bufs[self._obs_slot], self._hist_bufs[self._obs_slot ^ 1], layout)
+        self.num_obs = layout.width
+        self.obs_buf = self._hist_bufs[self._obs_slot]
 
     def _trimesh_contact_table(self):
         """mesh_type 'trimesh' with a slope threshold: the contact table of the slope-corrected mesh

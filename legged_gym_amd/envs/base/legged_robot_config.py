@@ -159,6 +159,16 @@ class LeggedRobotCfg(BaseConfig):
         contact_force_scale = 0.01
         torque_scale = 0.05
 
+    class history:
+        """A proprioceptive history behind the actor's observations (no reference counterpart).
+        frames = H > 0 makes the env's row `[obs | frame_1 | ... | frame_H]` (envs/base/history.py):
+        frame_k is the first frame_width entries of the row the env returned k steps ago, zeros
+        before the episode's first row; env.num_obs becomes num_observations + H * frame_width.
+        The default width is the 48-entry proprioceptive block every robot here shares.  frames = 0:
+        no history, nothing changes."""
+        frames = 0
+        frame_width = 48
+
     class viewer:  # ref :190-194
         ref_env = 0
         pos = [10, 0, 6]

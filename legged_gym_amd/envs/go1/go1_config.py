@@ -5,6 +5,8 @@
 with the 187-point height scan (235-dim obs), as SURVEY.md §8 defines it.
 `Go1RoughAsymCfg` is that task with an asymmetric actor-critic: the critic reads the privileged
 row (noise-free observations + the randomised friction / base mass + foot contacts).
+`Go1RoughHistCfg` is go1_rough with an observation history, registered as
+go1_rough_hist; `Go1RoughAsymHistCfg` pairs the history with the privileged critic (not registered).
 """
 from legged_gym_amd.envs.base.legged_robot_config import LeggedRobotCfg, LeggedRobotCfgPPO
 
@@ -101,3 +103,20 @@ class Go1RoughAsymCfg(Go1RoughTerrainCfg):
     class domain_rand(Go1RoughTerrainCfg.domain_rand):
         randomize_friction = True
         randomize_base_mass = True
+
+
+class Go1RoughHistCfg(Go1RoughTerrainCfg):
+    """go1_rough with a proprioceptive history (no reference counterpart): the observation row is the
+    noisy 235 observations plus the leading 48 entries of the last 5 rows (235 + 5 * 48 = 475,
+    envs/base/history.py).  No privileged row: the critic reads the same 475 entries."""
+    class history(Go1RoughTerrainCfg.history):
+        frames = 5
+
+
+class Go1RoughAsymHistCfg(Go1RoughAsymCfg):
+    """go1_rough_asym with that history for the actor: actor 475 wide, critic the 253-wide privileged
+    row.  Not in the registry (go1_rough_asym is the one registered task with a privileged row);
+    register it under a name of your own: task_registry.register(name, Go1, Go1RoughAsymHistCfg(),
+    Go1RoughCfgPPO())."""
+    class history(Go1RoughAsymCfg.history):
+        frames = 5

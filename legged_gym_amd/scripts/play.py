@@ -6,6 +6,7 @@ term over the first episode length, as play.py:73-121.
 
     python -m legged_gym_amd.scripts.play --task go1_rough [--load_run RUN --checkpoint IT] [--steps 1000]
 """
+import copy
 import os
 import sys
 
@@ -19,7 +20,10 @@ EXPORT_POLICY = True
 
 
 def play(args, steps=1000):
-    env_cfg, train_cfg = task_registry.get_cfgs(name=args.task)
+    # copies: the registry's configs are objects shared by everything in the process, and the
+    # overrides below are play's alone (on the shared objects they outlived play: a later reader of
+    # the registry, such as a test of a task's registered config, saw friction randomisation off)
+    env_cfg, train_cfg = copy.deepcopy(task_registry.get_cfgs(name=args.task))
     env_cfg.env.num_envs = min(env_cfg.env.num_envs, 25)          # play.py:50-60 overrides
     env_cfg.terrain.num_rows = 5
     env_cfg.terrain.num_cols = 5

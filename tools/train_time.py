@@ -1,8 +1,8 @@
 """Wall time per training iteration of OnPolicyRunner.learn as scripts/train.py runs it (with a log
-directory) and as bench.py runs it (without): go1_rough, 4096 envs.
+directory) and as bench.py runs it (without): go1_rough (or --task), 4096 envs.
 
     python tools/train_time.py [--configs logged,logged_old,logged_defer,unlogged] [--iters 50]
-                               [--warmup 10] [--windows 5]
+                               [--warmup 10] [--windows 5] [--task go1_rough]
 
 Configurations (one runner with a temporary log directory, one without, on one env):
     logged        log directory, device episode statistics (the default path)
@@ -40,11 +40,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--num_envs", type=int, default=4096)
+    ap.add_argument("--task", default="go1_rough")
     a = ap.parse_args()
     configs = a.configs.split(",")
     assert all(c in ENV for c in configs), f"configurations: {sorted(ENV)}"
     assert torch.cuda.is_available(), "train_time.py measures on the GPU"
-    task = "go1_rough"
+    task = a.task
     env_cfg, train_cfg = task_registry.get_cfgs(task)
     env_cfg.env.num_envs = a.num_envs
     cli = get_args(["--sim_device", "cuda:0", "--rl_device", "cuda:0", "--headless", "--task", task])
