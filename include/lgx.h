@@ -754,8 +754,12 @@ int lgx_adam_clip(float* p, float* g, float* m, float* v, int64_t n, float* part
 /* algo: LGX_GEMM_ALGO_DEFAULT = the process default (env LGX_GEMM_ALGO = "split" | "f32",
  * "split" when unset); LGX_GEMM_ALGO_F32 = v_mfma_f32_32x32x2_f32 (exact f32 fmaf chain);
  * LGX_GEMM_ALGO_SPLIT_BF16 = each f32 operand split into three RNE bf16 limbs, the six limb
- * products of order <= 2 on v_mfma_f32_32x32x16_bf16 with f32 accumulation (f32-accurate:
- * dropped terms and split residues <= ~2^-25 |a b|, below one f32 product rounding) */
+ * products of order <= 2 on v_mfma_f32_32x32x16_bf16 with f32 accumulation (f32-accurate: the
+ * three limbs reproduce a normal f32 exactly, the dropped terms are <= 2.04 * 2^-24 |a b| and
+ * the accumulator's roundings <= 5 * 2^-24 |a b|, so a single product is within 2^-21 |a b|
+ * - measured <= 2.7 * 2^-24 -, and dense sums match the exact-f32 path's error; derived in
+ * tests/split_products_ref.py and held on every split-bf16 kernel - lgx_gemm_nt, lgx_gemm_tn,
+ * lgx_mlp_x3_forward - by tests/test_gpu_split_products.py) */
 #define LGX_GEMM_ALGO_DEFAULT 0
 #define LGX_GEMM_ALGO_F32 1
 #define LGX_GEMM_ALGO_SPLIT_BF16 2

@@ -3,15 +3,18 @@
 //
 // Every f32 operand is split, round-to-nearest, into three bf16 limbs
 //   x = x0 + x1 + x2 + e,   x0 = bf16(x), x1 = bf16(x - x0), x2 = bf16(x - x0 - x1),
-//   |x1| <= 2^-8 |x0|, |x2| <= 2^-8 |x1|, |e| <= 2^-24 |x|   (both subtractions are exact in f32),
+//   |x1| <= 2^-8 |x0|, |x2| <= 2^-8 |x1|, e = 0 for a normal f32   (both subtractions are exact in f32),
 // and a*b is evaluated as the six limb products of order <= 2,
 //   a0 b0 + (a0 b1 + a1 b0) + (a0 b2 + a1 b1 + a2 b0),
 // each product of two bf16 limbs exact in the f32 accumulator.  The dropped terms (a1 b2, a2 b1,
-// a2 b2) and the split residues are at the level of one f32 product rounding (2^-24 |a b|; a few
-// times that in the worst case, far less on average since the limb ratios are spread over the
-// half-ulp range), and each 16-k MFMA rounds the accumulator once per limb product (6 roundings
-// per 16 k against 16 for the fmaf chain): the result is f32-accurate (tests/test_gpu_gemm.py:
-// max / mean error vs float64 within 1.25x of the exact-f32 MFMA's on the same operands).
+// a2 b2) are <= 2.04 * 2^-24 |a b| (far less on average since the limb ratios are spread over the
+// half-ulp range) and the accumulator's roundings of one product <= 5 * 2^-24 |a b|: a single
+// product is within 2^-21 |a b| (tests/split_products_ref.py derives it; measured <= 2.7 * 2^-24
+// on every split-bf16 kernel).  Each 16-k MFMA rounds the accumulator once per limb product (6
+// roundings per 16 k against 16 for the fmaf chain): the result is f32-accurate
+// (tests/test_gpu_split_products.py: every single product within 2^-21, and max / mean error of
+// dense sums vs float64 within 1.25x of the exact-f32 MFMA's on the same operands, on this
+// kernel, the pipelined one, lgx_gemm_tn's and the rollout MLP's).
 // 6 MFMAs at 1/16 the cost of the f32 MFMA's 8 per 16 k: a 2.67x higher arithmetic roof
 // (417 TF/s of f32 products against 157 TF/s).
 //

@@ -5,7 +5,8 @@
 // the slices into the flat gradient.  Replaces the library f32 bmm over slices.
 //
 // Same f32-accurate arithmetic as the split-bf16 path of lgx_gemm_nt (lgx_gemm_split.hip): both
-// operands split into three RNE bf16 limbs, six limb products on v_mfma_f32_32x32x16_bf16.
+// operands split into three RNE bf16 limbs, six limb products on v_mfma_f32_32x32x16_bf16 (a single
+// product within 2^-21 |a b| on each of the six kernels below: tests/test_gpu_split_products.py).
 // Both operands are row-major in m (the reduction index), so the MFMA fragments (8 consecutive m
 // of one column per lane) are column reads of the staged tiles:
 //   * each 32-row stage of A (128 columns n) and B (128 columns c) is loaded as f32 (16-byte row

@@ -3,7 +3,8 @@
 // inference of OnPolicyRunner.learn's rollout loop), both networks in ONE launch (blockIdx.y).
 // Same arithmetic as the PPO-update GEMMs (lgx_gemm_split.hip): every f32 operand as three RNE
 // bf16 limbs, the six limb products of order <= 2 on v_mfma_f32_32x32x16_bf16 with f32
-// accumulation (f32-accurate); 2.67x the product rate of lgx_mlp_forward_kernel's f32 MFMA.
+// accumulation (f32-accurate: a single product within 2^-21 |a b|, tests/test_gpu_split_products.py);
+// 2.67x the product rate of lgx_mlp_forward_kernel's f32 MFMA.
 //
 //   * 32 rows per workgroup, 8 waves.  The rows' activations stay in LDS across all layers as
 //     bf16 limb images [limb][32 rows][Kp] (Kp = width rounded up to 64, 16-byte row pad), split

@@ -344,12 +344,20 @@ def test_mlp_forward_matches_torch(gpu, dims):
     assert ok, f"mlp forward max err {e}"
 
 
+# the max error of the f32 MFMA kernel (lgx_mlp_forward) against float64 on the same data, as measured on an
+# MI355X (the split-bf16 kernel's own: 1.561e-6, 7.260e-7, 1.107e-6, 6.338e-7, 4.902e-7)
+MLP_F32_ERR = {(235, 512, 256, 128, 12): 1.5341e-6, (235, 512, 256, 128, 1): 5.9797e-7,
+               (48, 512, 256, 128, 12): 1.4927e-6, (7, 33, 5): 8.1410e-7, (30, 128, 128, 128, 3): 6.3584e-7}
+
+
 @pytest.mark.parametrize("dims,act,rows", [((235, 512, 256, 128, 12), 1, 4096), ((235, 512, 256, 128, 1), 1, 37),
                                            ((48, 512, 256, 128, 12), 1, 1000), ((7, 33, 5), 1, 1000),
                                            ((30, 128, 128, 128, 3), 2, 777)])
 def test_mlp_x3_forward_matches_torch(gpu, dims, act, rows):
     """lgx_mlp_x3_forward (split-bf16 products, weights from lgx_mlp_x3_split) against a float64
-    torch forward: f32-level agreement, ragged row tiles, widths off the 32 / 64 paddings."""
+    torch forward: within 1.25x the error of the f32 kernel on the same data (each limb product is
+    held to f32 accuracy by test_gpu_split_products.py), ragged row tiles, widths off the 32 / 64
+    paddings."""
     from legged_gym_amd.sim import abi
     from legged_gym_amd.sim import lib as lgxlib
     lib = lgxlib.load()
@@ -383,7 +391,9 @@ def test_mlp_x3_forward_matches_torch(gpu, dims, act, rows):
     lgxlib.check(lib.lgx_mlp_x3_forward(d, 1, stream), "mlp_x3_forward")
     torch.cuda.synchronize()
     err = (y.cpu().double() - h).abs().max().item()
-    assert err <= 2e-5 * max(1.0, h.abs().max().item()), f"mlp x3 max err {err:.3e}"
+    e32 = MLP_F32_ERR[dims]
+    assert 1.25 * e32 <= 2e-5 * max(1.0, h.abs().max().item())      # never looser than the earlier tolerance
+    assert err <= 1.25 * e32, f"mlp x3 max err {err:.3e} > 1.25 x {e32:.3e}"
 
 
 def test_mlp_x3_falls_back_when_lds_is_short(gpu):
