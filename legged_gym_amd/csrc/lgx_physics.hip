@@ -670,7 +670,8 @@ LGX_DEV float psum(float v) {
 
 // PP lanes per leg, 4*PP lanes per env: lane = env*4PP + p*4 + leg.  Every lane of a leg
 // group computes the leg's dynamics (identical values, no extra time); the contact candidates
-// of the leg are dealt round-robin over its PP lanes and their J^T W J terms reduced with
+// of the leg are dealt round-robin over its PP lanes (each lane then visits only its penetrating
+// ones, from a mask built once per substep) and their J^T W J terms reduced with
 // shuffles, so the serial contact work per lane shrinks PP-fold while the chip gets PP x
 // more waves (4096 envs x 16 lanes = 1024 waves for PP = 4: all 4 SIMDs of every CU busy).
 template <int PP>
@@ -723,6 +724,12 @@ lgx_physics_kernel(const lgx_dev_model* __restrict__ DMg, const lgx_env_params* 
   const int ec = valid ? e : N - 1;  // inactive lanes compute on a clamped env, never store
 
   LGX_CLK_DECL(12)
+#ifdef LGX_PHASE_CLOCK
+  // contact-loop bodies this wave executed (a body runs when any lane has a contact in the trip):
+  // pass-0 assembly, pass-1 assembly, classification, force report; printed with the phase clock and
+  // summarised by tools/phase_clock_bodies.py
+  unsigned lgx_bodies[4] = {0u, 0u, 0u, 0u};
+#endif
   const float dt = M->sim_dt;
   // ---- load state
   const float* rs = B.root_states + (int64_t)ec * 13;
@@ -1193,6 +1200,21 @@ lgx_physics_kernel(const lgx_dev_model* __restrict__ DMg, const lgx_env_params* 
       }
       wave_lds_sync();
     }
+    // this lane's active list for the substep (bit = own slot): every own slot's status is 0 or 1 by
+    // now (all slots read before the first is used; the slots past the leg's candidates hold nothing
+    // and are masked).  The contact loops visit the set bits in ascending slot order - the contacts
+    // and the order of the walk over every slot, so the sums are bitwise the same - without the read
+    // and wait of each empty slot, and a wave runs as many trips as its fullest lane has contacts
+    // instead of one for every slot index some lane fills.
+    uint32_t own_act = 0;
+    {
+      float sx[SLOTS];
+#pragma unroll
+      for (int sl = 0; sl < SLOTS; ++sl) sx[sl] = slot_state[sl][tid].x;
+#pragma unroll
+      for (int sl = 0; sl < SLOTS; ++sl)   // bitwise and: `&&` lets the compiler sink the read under the bound test
+        own_act |= ((unsigned)(pl + PP * sl < npts) & (unsigned)(sx[sl] != 0.f)) << sl;
+    }
     LGX_CLK(10);
     float xb[6];
     f3 xl;
@@ -1205,15 +1227,26 @@ lgx_physics_kernel(const lgx_dev_model* __restrict__ DMg, const lgx_env_params* 
 #pragma unroll
       for (int i = 0; i < 6; ++i) L.D[i] = 0.f;
       L.rl[0] = L.rl[1] = L.rl[2] = 0.f;
-      for (int c = pl, sl = 0; c < maxpts; c += PP, ++sl) {
-        if (c >= npts) break;
+      // one trip per contact of the wave's fullest lane (wave-uniform exit); a lane without a
+      // contact left reads its first cell (always-valid LDS) and discards it
+      uint32_t w = own_act;
+#pragma unroll 1
+      for (int trip = 0; trip < SLOTS; ++trip) {
+        if (__ballot(w != 0u) == 0) break;
+        const bool on = w != 0u;
+        const int sl = on ? __builtin_ctz(w) : 0;
+        w &= w - 1;
         const float4 st = slot_state[sl][tid];
-        if (st.x == 0.f) continue;  // separated (pass 1: in pass 0's classification)
         const float4 gp = geo_p[sl][tid], gn = geo_n[sl][tid];
+        const bool use = on && st.x != 0.f;  // separated (pass 1: in pass 0's classification)
+        const int db = M->point_dyn[use ? (int)gn.w : 0];
+#ifdef LGX_PHASE_CLOCK
+        if (__ballot(use)) ++lgx_bodies[pass];
+#endif
+        if (!use) continue;
         const f3 Pc = mk3(gp.x, gp.y, gp.z);
         const float depth = gp.w;
         const f3 n = mk3(gn.x, gn.y, gn.z);
-        const int db = M->point_dyn[(int)gn.w];
         const int k = db == 0 ? -1 : (db - 1) % 3;
         float wt = (pass == 0 || st.x == 1.f) ? dt * ct : 0.f;
         f3 f = (dt * kn * depth) * n;
@@ -1243,15 +1276,25 @@ lgx_physics_kernel(const lgx_dev_model* __restrict__ DMg, const lgx_env_params* 
         Vl[0] = add(Vb, scale(xl.x, S[0]));
         Vl[1] = add(Vl[0], scale(xl.y, S[1]));
         Vl[2] = add(Vl[1], scale(xl.z, S[2]));
-        for (int c = pl, sl = 0; c < maxpts; c += PP, ++sl) {
-          if (c >= npts) break;
+        uint32_t w = own_act;
+#pragma unroll 1
+        for (int trip = 0; trip < SLOTS; ++trip) {
+          if (__ballot(w != 0u) == 0) break;
+          const bool on = w != 0u;
+          const int sl = on ? __builtin_ctz(w) : 0;
+          w &= w - 1;
           float4 st = slot_state[sl][tid];
-          if (st.x == 0.f) continue;
           const float4 gp = geo_p[sl][tid], gn = geo_n[sl][tid];
+          const bool use = on && st.x != 0.f;
+          const int pi = use ? (int)gn.w : 0;
+          const int db = M->point_dyn[pi];
+          const int rep = M->point_report[pi];
+#ifdef LGX_PHASE_CLOCK
+          if (__ballot(use)) ++lgx_bodies[2 + pass];
+#endif
+          if (!use) continue;
           const f3 Pc = mk3(gp.x, gp.y, gp.z), n = mk3(gn.x, gn.y, gn.z);
           const float depth = gp.w;
-          const int pi = (int)gn.w;
-          const int db = M->point_dyn[pi];
           const int k = db == 0 ? -1 : (db - 1) % 3;
           sv V = db == 0 ? Vb : sel3(k, Vl[0], Vl[1], Vl[2]);
           f3 vp = V.l + cross(V.a, Pc);
@@ -1270,7 +1313,6 @@ lgx_physics_kernel(const lgx_dev_model* __restrict__ DMg, const lgx_env_params* 
             fn = fmaxf(fn, 0.f);
             f3 ft = st.x == 1.f ? (-ct) * vt : mk3(st.y, st.z, st.w);
             f3 F = fn * n + ft;
-            int rep = M->point_report[pi];
             if (rep == 0) cf_base = cf_base + F;
             else {
               int r = rep - (1 + 4 * leg);
@@ -1372,6 +1414,13 @@ lgx_physics_kernel(const lgx_dev_model* __restrict__ DMg, const lgx_env_params* 
   }
   LGX_CLK(7);
   LGX_CLK_PRINT("physics", 12)
+#if defined(LGX_PHASE_CLOCK) && !defined(LGX_PHASE_CLOCK_BUF)
+  if (LGX_CLK_WHO)
+    printf("physics bodies: b=%d pass0=%u pass1=%u classify=%u report=%u\n", (int)blockIdx.x, lgx_bodies[0],
+           lgx_bodies[1], lgx_bodies[2], lgx_bodies[3]);
+#elif defined(LGX_PHASE_CLOCK)
+  (void)lgx_bodies;
+#endif
 }
 
 // ground_contact for a batch of world points (test entry lgx_ground_contact): q[k] = (x, y, z, r)

@@ -1,6 +1,7 @@
 #!/bin/bash
 # Build an instrumented copy of liblgx (per-phase clock64 sums of block 0 / thread 0, printed by
 # the kernels) into tools/_tmp/clock/ — run on the CPU side; use with LGX_LIB_PATH=tools/_tmp/clock/liblgx.so.
+# The physics kernel also prints the contact-loop bodies its wave executed (tools/phase_clock_bodies.py sums them up).
 set -e
 cd "$(dirname "$0")/.."
 mkdir -p tools/_tmp/clock
