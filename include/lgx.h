@@ -374,6 +374,35 @@ int lgx_bind_obs_history(lgx_sim* sim, float* row, const float* prev_row, const 
  * with no history bound. */
 int lgx_rebind_obs_history(lgx_sim* sim, float* row, const float* prev_row);
 
+/* Per-env actuator randomisation, read by every physics launch (lgx_step / lgx_step_from /
+ * lgx_drive_inputs / lgx_simulate) while bound (no reference counterpart).  Device
+ * tables owned by the caller, who may rewrite them in place between launches; a NULL table means
+ * 1, 1 and 0:
+ *   kp_scale f32 [N,12]  drive stiffness of env e, joint j: kp_e = kp * kp_scale[e][j], one rounded
+ *                        product formed once per launch (kp = lgx_model.kp with LGX_CTRL_POS_DRIVE,
+ *                        lgx_env_params.p_gains with LGX_CTRL_P / LGX_CTRL_V); every expression
+ *                        that reads the gain - the implicit drive, the explicit torque, the reported
+ *                        torque, the effort-limit test - reads kp_e
+ *   kd_scale f32 [N,12]  the same for the damping (lgx_model.kd / lgx_env_params.d_gains)
+ *   lag      i32 [N]     action latency in substeps, clamped to [0, substeps of the launch]: in a
+ *                        launch that takes actions, substep s of env e acts on the previous launch's
+ *                        clipped actions while s < lag[e] (position target, P / V / T laws, the Go1
+ *                        actuator history's position error), then on this launch's; the launch ends
+ *                        with prev[e] = this launch's clipped actions.  prev is the sim's own [N,12]
+ *                        buffer, zeroed at bind and read as zero for an env whose episode_length is
+ *                        0 when the launch starts (as sea_h: an episode that starts here has no
+ *                        earlier action).  The bound actions buffer still receives this launch's
+ *                        clipped actions, dof_targets the last substep's target.
+ * A NULL desc or three NULL tables unbind (prev is freed; the launches are then the ones of a sim
+ * that never bound).  LGX_EINVAL (message in lgx_last_error) for a null sim, a sim on the dense
+ * physics kernel (leg_dof == 6), LGX_CTRL_SEA, or gain tables with LGX_CTRL_T. */
+typedef struct lgx_actuator_rand_desc {
+  const float* kp_scale;
+  const float* kd_scale;
+  const int32_t* lag;
+} lgx_actuator_rand_desc;
+int lgx_bind_actuator_rand(lgx_sim* sim, const lgx_actuator_rand_desc* desc);
+
 /* Data-parallel gradient all-reduce over RCCL (SURVEY §8(b) lgx_allreduce_grads; §8(e): the
  * gradient average of a multi-GPU PPO update, one rank per GPU).  One communicator per rank,
  * created collectively from a unique id that rank 0 draws and the caller distributes (e.g. over

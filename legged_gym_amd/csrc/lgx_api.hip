@@ -45,6 +45,7 @@ struct lgx_sim {
   float* extras_snapshot;  // lgx_rebind_extras (NULL: no per-call copy)
   lgx_priv_args priv;      // lgx_bind_privileged_obs (buf NULL: no privileged row)
   lgx_hist_args hist;      // lgx_bind_obs_history (row NULL: no history; age is owned here)
+  lgx_act_rand_args arand; // lgx_bind_actuator_rand (prev NULL: no tables; prev is owned here)
   // Go1 actuator net off the critical path: its output (dVel) is not read by the step
   // (go1.py:71-73), so it runs on an auxiliary stream concurrently with post-physics and the
   // next policy forward; the next physics launch (which rewrites model_ins) waits for it.
@@ -206,6 +207,7 @@ int lgx_sim_create(const lgx_model* model, const lgx_env_params* params, const l
   s->extras_snapshot = nullptr;
   s->priv = lgx_priv_args{};
   s->hist = lgx_hist_args{};
+  s->arand = lgx_act_rand_args{};
   s->aux = nullptr;
   s->aux_in = s->aux_done = nullptr;
   s->aux_pending = false;
@@ -239,6 +241,7 @@ int lgx_sim_destroy(lgx_sim* s) {
   for (auto& v : s->ev) for (hipEvent_t e : v) (void)hipEventDestroy(e);
   for (hipEvent_t e : s->pool) (void)hipEventDestroy(e);
   (void)hipFree(s->hist.age);
+  (void)hipFree(s->arand.prev);
   (void)hipFree(s->d_model);
   (void)hipFree(s->d_params);
   delete s;
@@ -397,6 +400,31 @@ int lgx_rebind_obs_history(lgx_sim* s, float* row, const float* prev) {
   return 0;
 }
 
+int lgx_bind_actuator_rand(lgx_sim* s, const lgx_actuator_rand_desc* d) {
+  if (!s) return fail(LGX_EINVAL, "lgx_bind_actuator_rand: null sim");
+  if (!d || (!d->kp_scale && !d->kd_scale && !d->lag)) {
+    int rc = s->arand.prev ? hip_check(hipFree(s->arand.prev), "lgx_bind_actuator_rand: hipFree(prev)") : 0;
+    s->arand = lgx_act_rand_args{};
+    return rc;
+  }
+  if (s->dense) return fail(LGX_EINVAL, "lgx_bind_actuator_rand: the dense physics kernel (leg_dof 6) has no actuator tables");
+  const int ctrl = s->params.control_type;
+  if (ctrl == LGX_CTRL_SEA) return fail(LGX_EINVAL, "lgx_bind_actuator_rand: LGX_CTRL_SEA has no actuator tables");
+  if (ctrl == LGX_CTRL_T && (d->kp_scale || d->kd_scale))
+    return fail(LGX_EINVAL, "lgx_bind_actuator_rand: LGX_CTRL_T has no gains to scale");
+  // a (re)bind starts every env without an earlier action: allocate once, zero every time.  A setup
+  // call: the device is drained before and after the memset, so it is ordered against launches on any stream
+  const size_t bytes = sizeof(float) * (size_t)s->params.num_envs * LGX_NUM_DOF;
+  float* prev = s->arand.prev;
+  if (!prev) {
+    if (int rc = hip_check(hipMalloc(&prev, bytes), "lgx_bind_actuator_rand: hipMalloc(prev)")) return rc;
+  }
+  s->arand = lgx_act_rand_args{d->kp_scale, d->kd_scale, d->lag, prev};
+  if (int rc = hip_check(hipDeviceSynchronize(), "lgx_bind_actuator_rand: hipDeviceSynchronize")) return rc;
+  if (int rc = hip_check(hipMemset(prev, 0, bytes), "lgx_bind_actuator_rand: hipMemset(prev)")) return rc;
+  return hip_check(hipDeviceSynchronize(), "lgx_bind_actuator_rand: hipDeviceSynchronize");
+}
+
 int lgx_rebind_extras(lgx_sim* s, float* snapshot) {
   if (!s) return fail(LGX_EINVAL, "lgx_rebind_extras: null sim");
   s->extras_snapshot = snapshot;
@@ -417,6 +445,9 @@ int lgx_sync_aux(lgx_sim* s, void* stream) {
 
 // the physics launch of a sim: the arrowhead kernel, or the dense one (lgx_sim.dense)
 static int physics(lgx_sim* s, int32_t nsub, int32_t from_actions, const float* actions, hipStream_t st, int32_t frozen) {
+  if (s->arand.prev)   // actuator tables bound (never on the dense kernel: lgx_bind_actuator_rand)
+    return lgx_launch_physics_rand(s->d_model, s->d_params, s->bufs, s->params.num_envs, nsub, from_actions, actions,
+                                   st, frozen, s->pp, s->arand);
   return s->dense ? lgx_launch_physics_dense(s->d_model, s->d_params, s->bufs, s->params.num_envs, nsub, from_actions,
                                              actions, st, frozen, s->num_points)
                   : lgx_launch_physics(s->d_model, s->d_params, s->bufs, s->params.num_envs, nsub, from_actions, actions,

@@ -26,6 +26,21 @@ int lgx_physics_pp(int32_t n_envs);   // lanes per leg of the physics launch at 
 int lgx_launch_physics(const lgx_dev_model* dm, const lgx_env_params* dp, const lgx_buffers& b, int32_t n_envs,
                        int32_t nsub, int32_t from_actions, const float* act_src, hipStream_t stream, int32_t frozen,
                        int pp);
+// the per-env actuator tables of a sim (lgx_bind_actuator_rand, checked there), passed by value to
+// the physics launches of a sim that bound them; prev == nullptr: nothing bound.  kp_scale / kd_scale
+// [N,12] and lag [N] are the caller's (each may be nullptr: 1, 1, 0), prev [N,12] is the sim's: the
+// clipped actions of the last launch that took actions
+struct lgx_act_rand_args {
+  const float* kp_scale;
+  const float* kd_scale;
+  const int32_t* lag;
+  float* prev;
+};
+// the same launch with the tables bound (ar.prev != nullptr; lgx_physics_rand.hip): the
+// lgx_physics_kernel<PP, lgx_act_rand_args> instantiations
+int lgx_launch_physics_rand(const lgx_dev_model* dm, const lgx_env_params* dp, const lgx_buffers& b, int32_t n_envs,
+                            int32_t nsub, int32_t from_actions, const float* act_src, hipStream_t stream,
+                            int32_t frozen, int pp, const lgx_act_rand_args& ar);
 // the dense joint-space kernel (lgx_physics.hip): leg_dof == 6 robots, or any with LGX_PHYS_DENSE=1
 int lgx_launch_physics_dense(const lgx_dev_model* dm, const lgx_env_params* dp, const lgx_buffers& b, int32_t n_envs,
                              int32_t nsub, int32_t from_actions, const float* act_src, hipStream_t stream,

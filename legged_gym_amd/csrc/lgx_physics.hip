@@ -674,10 +674,31 @@ LGX_DEV float psum(float v) {
 // ones, from a mask built once per substep) and their J^T W J terms reduced with
 // shuffles, so the serial contact work per lane shrinks PP-fold while the chip gets PP x
 // more waves (4096 envs x 16 lanes = 1024 waves for PP = 4: all 4 SIMDs of every CU busy).
-template <int PP>
+//
+// AR: empty (lgx_physics_kernel<PP>: the kernel of a sim with no actuator tables bound - no extra
+// argument, no extra code) or lgx_act_rand_args (lgx_bind_actuator_rand; instantiated in
+// lgx_physics_rand.hip): per-env drive gains kp_e = kp * kp_scale[e][j], kd_e = kd * kd_scale[e][j],
+// each formed once per launch, and an action latency of lag[e] substeps - substep s of a launch that
+// takes actions uses the previous launch's clipped actions while s < lag[e].  The six gains, the three
+// previous actions and the lag of a leg sit in an LDS row like leg_sys (every lane of the leg stores
+// the same values), not in ten more live VGPRs: the kernel runs at its register ceiling.
+// the gains and the substep's action as the expressions of the kernel read them: the model's / the
+// params' / this launch's, or with RAND this leg's LDS row / the delayed action (RAND is a constant:
+// only one arm is compiled)
+#define PHYS_KP(k, j) (RAND ? arow[k] : M->kp[j])
+#define PHYS_KD(k, j) (RAND ? arow[3 + (k)] : M->kd[j])
+#define PHYS_PG(k, j) (RAND ? arow[k] : P->p_gains[j])
+#define PHYS_DG(k, j) (RAND ? arow[3 + (k)] : P->d_gains[j])
+#define PHYS_AE(k) (RAND ? ae_lag[k] : act[k])
+LGX_DEV lgx_act_rand_args act_rand_of() { return lgx_act_rand_args{nullptr, nullptr, nullptr, nullptr}; }
+LGX_DEV lgx_act_rand_args act_rand_of(const lgx_act_rand_args& a) { return a; }
+
+template <int PP, typename... AR>
 __global__ void __launch_bounds__(64 * PP, LGX_PHYS_WAVES_PER_SIMD)
 lgx_physics_kernel(const lgx_dev_model* __restrict__ DMg, const lgx_env_params* __restrict__ P, lgx_buffers B,
-                   int32_t nsub, int32_t from_actions, const float* __restrict__ act_src, int32_t frozen) {
+                   int32_t nsub, int32_t from_actions, const float* __restrict__ act_src, int32_t frozen, AR... ar) {
+  static_assert(sizeof...(AR) <= 1, "at most the actuator tables");
+  constexpr bool RAND = sizeof...(AR) == 1;
   constexpr int PHYS_BLOCK = 64 * PP;               // 16 envs per workgroup
   constexpr int LPE = 4 * PP;                       // lanes per env
   constexpr int SLOTS = (MAX_LANE_PTS + PP - 1) / PP;
@@ -758,6 +779,25 @@ lgx_physics_kernel(const lgx_dev_model* __restrict__ DMg, const lgx_env_params* 
 #pragma unroll
     for (int k = 0; k < 3; ++k) act[k] = clampf(a[k], -P->clip_actions, P->clip_actions);
   }
+  // RAND: this leg's row - kp_e (3), kd_e (3), the previous launch's clipped actions (3; zero for an
+  // env whose episode starts here, as lgx_buffers.sea_h is read), the lag clamped to [0, nsub]
+  float* arow = nullptr;
+  if constexpr (RAND) {
+    __shared__ float ar_lds[ENVS * 4][12];
+    arow = ar_lds[lg];
+    const lgx_act_rand_args R = act_rand_of(ar...);
+    const bool had_action = from_actions && B.episode_length[ec] != 0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const int j = 3 * leg + k;
+      const float kp = ctrl == LGX_CTRL_POS_DRIVE ? M->kp[j] : P->p_gains[j];
+      const float kd = ctrl == LGX_CTRL_POS_DRIVE ? M->kd[j] : P->d_gains[j];
+      arow[k] = __fmul_rn(kp, R.kp_scale ? R.kp_scale[(int64_t)ec * 12 + j] : 1.0f);
+      arow[3 + k] = __fmul_rn(kd, R.kd_scale ? R.kd_scale[(int64_t)ec * 12 + j] : 1.0f);
+      arow[6 + k] = had_action ? R.prev[(int64_t)ec * 12 + j] : 0.f;
+    }
+    arow[9] = __int_as_float(R.lag ? min(max(R.lag[ec], 0), nsub) : 0);
+  }
   if (ctrl == LGX_CTRL_POS_DRIVE) {
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
@@ -829,12 +869,27 @@ lgx_physics_kernel(const lgx_dev_model* __restrict__ DMg, const lgx_env_params* 
 
   LGX_CLK(6);
   for (int s = 0; s < nsub; ++s) {
+    // the action this substep acts on: RAND, the previous launch's while s < lag (and the position
+    // target that follows from it, so dof_targets receives the last substep's)
+    float ae_lag[3];
+    if constexpr (RAND) {
+      const bool late = from_actions && s < __float_as_int(arow[9]);   // act is read only where from_actions
+#pragma unroll
+      for (int k = 0; k < 3; ++k) ae_lag[k] = late ? arow[6 + k] : act[k];
+      if (from_actions && ctrl == LGX_CTRL_POS_DRIVE) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          int j = 3 * leg + k;
+          tgt[k] = clampf(PHYS_AE(k) * P->action_scale + P->default_dof_pos[j], P->soft_lower[j], P->soft_upper[j]);
+        }
+      }
+    }
     // ---- Go1 actuator-net history (go1.py:79-98), model_ins per substep
     if (use_hist) {
 #pragma unroll
       for (int k = 0; k < 3; ++k) {
         int j = 3 * leg + k;
-        float pe = act[k] - th[k];
+        float pe = PHYS_AE(k) - th[k];
         float pes = (pe - P->act_pos_err_mean[j]) / P->act_pos_err_std[j];
         float vs = (thd[k] - P->act_vel_mean[j]) / P->act_vel_std[j];
 #pragma unroll
@@ -882,10 +937,10 @@ lgx_physics_kernel(const lgx_dev_model* __restrict__ DMg, const lgx_env_params* 
 #pragma unroll
       for (int k = 0; k < 3; ++k) {
         int j = 3 * leg + k;
-        float a = act[k] * P->action_scale, t;
-        if (ctrl == LGX_CTRL_P) t = P->p_gains[j] * (a + P->default_dof_pos[j] - th[k]) - P->d_gains[j] * thd[k];
+        float a = PHYS_AE(k) * P->action_scale, t;
+        if (ctrl == LGX_CTRL_P) t = PHYS_PG(k, j) * (a + P->default_dof_pos[j] - th[k]) - PHYS_DG(k, j) * thd[k];
         else if (ctrl == LGX_CTRL_V)
-          t = P->p_gains[j] * (a - thd[k]) - P->d_gains[j] * (thd[k] - B.last_dof_vel[(int64_t)ec * 12 + j]) / dt;
+          t = PHYS_PG(k, j) * (a - thd[k]) - PHYS_DG(k, j) * (thd[k] - B.last_dof_vel[(int64_t)ec * 12 + j]) / dt;
         else t = a;
         tex[k] = clampf(t, -P->torque_limits[j], P->torque_limits[j]);
       }
@@ -1015,7 +1070,7 @@ lgx_physics_kernel(const lgx_dev_model* __restrict__ DMg, const lgx_env_params* 
     for (int k = 0; k < 3; ++k) {
       int j = 3 * leg + k;
       // model reads first (LDS): a read inside a lane-dependent branch waits on its own round trip
-      const float kp = M->kp[j], kd = M->kd[j], eff = M->dof_effort[j];
+      const float kp = PHYS_KP(k, j), kd = PHYS_KD(k, j), eff = M->dof_effort[j];
       const float lo = M->dof_lower[j], hi = M->dof_upper[j], lk = M->limit_k, lc = M->limit_c;
       float g = 0.f;
       if (ctrl == LGX_CTRL_POS_DRIVE) {
@@ -1336,8 +1391,8 @@ lgx_physics_kernel(const lgx_dev_model* __restrict__ DMg, const lgx_env_params* 
       if (vl > 0.f) q2 = clampf(q2, -vl, vl);
       if (ctrl == LGX_CTRL_POS_DRIVE) {
         float eff = M->dof_effort[j];
-        float t = impl[k] ? M->kp[j] * (tgt[k] - th[k] - dt * qdn[k]) - M->kd[j] * qdn[k]
-                          : M->kp[j] * (tgt[k] - th[k]) - M->kd[j] * thd[k];
+        float t = impl[k] ? PHYS_KP(k, j) * (tgt[k] - th[k] - dt * qdn[k]) - PHYS_KD(k, j) * qdn[k]
+                          : PHYS_KP(k, j) * (tgt[k] - th[k]) - PHYS_KD(k, j) * thd[k];
         tq[k] = clampf(t, -eff, eff);
       } else {
         tq[k] = tex[k];
@@ -1367,6 +1422,10 @@ lgx_physics_kernel(const lgx_dev_model* __restrict__ DMg, const lgx_env_params* 
   if (from_actions) {
     float* ao = B.actions + (int64_t)e * 12 + leg * 3;
     ao[0] = act[0]; ao[1] = act[1]; ao[2] = act[2];
+    if constexpr (RAND) {   // the next launch's previous actions
+      float* po = act_rand_of(ar...).prev + (int64_t)e * 12 + leg * 3;
+      po[0] = act[0]; po[1] = act[1]; po[2] = act[2];
+    }
   }
   if (frozen) {
     if (ctrl == LGX_CTRL_POS_DRIVE && from_actions) {
@@ -1422,6 +1481,36 @@ lgx_physics_kernel(const lgx_dev_model* __restrict__ DMg, const lgx_env_params* 
   (void)lgx_bodies;
 #endif
 }
+
+// This file is compiled twice.  On its own it gives the kernels of a sim with no actuator tables bound
+// (and everything else below); lgx_physics_rand.hip includes it with LGX_PHYSICS_RAND defined and
+// gives the lgx_physics_kernel<PP, lgx_act_rand_args> instantiations and their launcher, nothing
+// else - kept out of this translation unit so that the kernels launched with nothing bound stay the
+// machine code they were (tools/kernel_code_diff.py; the note in lgx_envlogic.hip).
+#ifdef LGX_PHYSICS_RAND
+
+int lgx_launch_physics_rand(const lgx_dev_model* dm, const lgx_env_params* dp, const lgx_buffers& b, int32_t n_envs,
+                            int32_t nsub, int32_t from_actions, const float* act_src, hipStream_t stream,
+                            int32_t frozen, int ppx, const lgx_act_rand_args& ar) {
+  if (!ar.prev) return -1;
+  if (!act_src) act_src = b.actions;
+  const int blocks = (n_envs + 15) / 16;       // 16 envs per workgroup of 64*PP lanes
+  if (ppx == 8)
+    LGX_LAUNCH((lgx_physics_kernel<8, lgx_act_rand_args>), dim3(blocks), dim3(512), 0, stream, dm, dp, b, nsub,
+               from_actions, act_src, frozen, ar);
+  else if (ppx == 4)
+    LGX_LAUNCH((lgx_physics_kernel<4, lgx_act_rand_args>), dim3(blocks), dim3(256), 0, stream, dm, dp, b, nsub,
+               from_actions, act_src, frozen, ar);
+  else if (ppx == 2)
+    LGX_LAUNCH((lgx_physics_kernel<2, lgx_act_rand_args>), dim3(blocks), dim3(128), 0, stream, dm, dp, b, nsub,
+               from_actions, act_src, frozen, ar);
+  else
+    LGX_LAUNCH((lgx_physics_kernel<1, lgx_act_rand_args>), dim3(blocks), dim3(64), 0, stream, dm, dp, b, nsub,
+               from_actions, act_src, frozen, ar);
+  return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+#else  // !LGX_PHYSICS_RAND
 
 // ground_contact for a batch of world points (test entry lgx_ground_contact): q[k] = (x, y, z, r)
 // -> o[k] = (depth, nx, ny, nz); heights / table read from global memory (no LDS patch)
@@ -2060,3 +2149,5 @@ extern "C" int lgx_debug_clock(unsigned long long* out, int32_t nblocks) {
                              hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
 }
 #endif
+
+#endif  // LGX_PHYSICS_RAND

@@ -2,7 +2,8 @@
 
 go1 (configs C1/C2 defaults), go1_rough (C3/C4: trimesh + height scan), go1_rough_asym (go1_rough
 with a privileged critic: env.num_privileged_obs + cfg.privileged), go1_rough_hist (go1_rough with
-an observation history: cfg.history), go1_flat_bench (C2 as
+an observation history: cfg.history), go1_rough_actrand (go1_rough with per-env drive gains and
+action latency: cfg.actuator_rand), go1_flat_bench (C2 as
 BASELINE states it: PD, no domain randomisation), anymal_c_rough (C5), anymal_c_flat, and the
 remaining robots of the reference registry: anymal_b, a1, a1_src, aliengo and cassie (the biped:
 2 legs x 6 joints on the dense physics kernel).
@@ -21,14 +22,15 @@ from .cassie.cassie import Cassie
 from .cassie.cassie_config import CassieRoughCfg, CassieRoughCfgPPO
 from .base.legged_robot_config import LeggedRobotCfg, LeggedRobotCfgPPO
 from .go1.go1 import Go1
-from .go1.go1_config import (Go1FlatBenchCfg, Go1RoughAsymCfg, Go1RoughCfg, Go1RoughCfgPPO, Go1RoughHistCfg,
-                             Go1RoughTerrainCfg)
+from .go1.go1_config import (Go1FlatBenchCfg, Go1RoughActRandCfg, Go1RoughAsymCfg, Go1RoughCfg, Go1RoughCfgPPO,
+                             Go1RoughHistCfg, Go1RoughTerrainCfg)
 
 task_registry.register("go1", Go1, Go1RoughCfg(), Go1RoughCfgPPO())
 task_registry.register("go1_flat_bench", Go1, Go1FlatBenchCfg(), Go1RoughCfgPPO())
 task_registry.register("go1_rough", Go1, Go1RoughTerrainCfg(), Go1RoughCfgPPO())
 task_registry.register("go1_rough_asym", Go1, Go1RoughAsymCfg(), Go1RoughCfgPPO())
 task_registry.register("go1_rough_hist", Go1, Go1RoughHistCfg(), Go1RoughCfgPPO())
+task_registry.register("go1_rough_actrand", Go1, Go1RoughActRandCfg(), Go1RoughCfgPPO())
 task_registry.register("anymal_c_rough", Anymal, AnymalCRoughCfg(), AnymalCRoughCfgPPO())
 task_registry.register("anymal_c_flat", Anymal, AnymalCFlatCfg(), AnymalCFlatCfgPPO())
 task_registry.register("anymal_b", Anymal, AnymalBRoughCfg(), AnymalBRoughCfgPPO())

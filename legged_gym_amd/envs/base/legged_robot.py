@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from legged_gym_amd import LEGGED_GYM_ROOT_DIR
-from legged_gym_amd.envs.base import history, privileged
+from legged_gym_amd.envs.base import actuator_rand, history, privileged
 from legged_gym_amd.envs.base.base_task import BaseTask
 from legged_gym_amd.sim import abi
 from legged_gym_amd.sim.model import RobotAsset, build_model, resolve_asset_path
@@ -109,6 +109,14 @@ class LgxBackend:
     def rebind_obs_history(self, row, prev_row):
         self._check(self.lib.lgx_rebind_obs_history(self.handle, C.c_void_p(row.data_ptr()),
                                                     C.c_void_p(prev_row.data_ptr())), "lgx_rebind_obs_history")
+
+    def bind_actuator_rand(self, kp_scale, kd_scale, lag):
+        """lgx_bind_actuator_rand: per-env gain scales (float32 [N,12]) and action latency (int32 [N]) read
+        by every physics launch; a None table means 1, 1, 0; all None unbinds.  The caller keeps the
+        tensors alive and may rewrite them in place."""
+        p = lambda t: t.data_ptr() if t is not None else None
+        d = abi.LgxActuatorRandDesc(p(kp_scale), p(kd_scale), p(lag))
+        self._check(self.lib.lgx_bind_actuator_rand(self.handle, C.byref(d)), "lgx_bind_actuator_rand")
 
     def sync_aux(self):
         self._check(self.lib.lgx_sync_aux(self.handle, self.stream()), "lgx_sync_aux")
@@ -606,9 +614,11 @@ class LeggedRobot(BaseTask):
         self._obs_slot = 0
         layout = self._privileged_layout()
         hist_layout = self._history_layout()
+        tables = self._actuator_rand_tables()
         self._backend = self._make_backend(self._lgx_model, p, b)
         self._bind_privileged_obs(layout)
         self._bind_obs_history(hist_layout)
+        self._bind_actuator_rand(tables)
 
     def _privileged_layout(self):
         """The critic's row `[clean obs | cfg.privileged.terms]` (envs/base/privileged.py), or None
@@ -636,6 +646,25 @@ class LeggedRobot(BaseTask):
         self._backend.bind_privileged_obs(self._priv_bufs[self._obs_slot], layout,
                                           float(getattr(pcfg, "contact_force_scale", 0.01)),
                                           float(getattr(pcfg, "torque_scale", 0.05)))
+
+    def _actuator_rand_tables(self):
+        """cfg.actuator_rand's per-env tables (envs/base/actuator_rand.py): (kp_scale, kd_scale, lag), each
+        None when its flags are off; ValueError for a config that does not add up.  A generator of its
+        own, seeded from the env seed: no other draw moves."""
+        return actuator_rand.draw(getattr(self.cfg, "actuator_rand", None), self.num_envs, self.num_dof,
+                                  self.cfg.control.decimation, int(getattr(self.cfg, "seed", 1)), self.device)
+
+    def _bind_actuator_rand(self, tables):
+        """Publish the tables as env.kp_scale / env.kd_scale / env.action_lag and bind them to the physics
+        launches (lgx_bind_actuator_rand)."""
+        self.kp_scale, self.kd_scale, self.action_lag = tables
+        if all(t is None for t in tables):
+            return
+        if not hasattr(self._backend, "bind_actuator_rand"):
+            raise ValueError(f"actuator_rand: the backend {type(self._backend).__name__} cannot bind per-env "
+                             "actuator tables (the CPU oracle backend of the tests has none; the lgx backend "
+                             "reads them in its physics launch)")
+        self._backend.bind_actuator_rand(self.kp_scale, self.kd_scale, self.action_lag)
 
     def _history_layout(self):
         """The actor's row `[obs | cfg.history.frames frames]` (envs/base/history.py), or None

@@ -169,6 +169,21 @@ class LeggedRobotCfg(BaseConfig):
         frames = 0
         frame_width = 48
 
+    class actuator_rand:
+        """Per-env actuator randomisation (no reference counterpart; envs/base/actuator_rand.py, DESIGN.md
+        §4.1b): drawn once at creation, per env and per joint, uniform.  motor strength multiplies both
+        gains: kp_scale = strength * kp_factor, kd_scale = strength * kd_factor.  lag: whole substeps an
+        action waits before it reaches the joints, an inclusive integer range inside
+        [0, control.decimation] (decimation = one full control step).  All off: nothing changes."""
+        randomize_motor_strength = False
+        motor_strength_range = [0.9, 1.1]
+        randomize_kp = False
+        kp_factor_range = [0.8, 1.2]
+        randomize_kd = False
+        kd_factor_range = [0.8, 1.2]
+        randomize_lag = False
+        lag_substeps_range = [0, 4]   # inclusive integers, <= control.decimation
+
     class viewer:  # ref :190-194
         ref_env = 0
         pos = [10, 0, 6]

@@ -7,6 +7,8 @@ with the 187-point height scan (235-dim obs), as SURVEY.md §8 defines it.
 row (noise-free observations + the randomised friction / base mass + foot contacts).
 `Go1RoughHistCfg` is go1_rough with an observation history, registered as
 go1_rough_hist; `Go1RoughAsymHistCfg` pairs the history with the privileged critic (not registered).
+`Go1RoughActRandCfg` is go1_rough with per-env drive gains and action latency,
+registered as go1_rough_actrand.
 """
 from legged_gym_amd.envs.base.legged_robot_config import LeggedRobotCfg, LeggedRobotCfgPPO
 
@@ -111,6 +113,17 @@ class Go1RoughHistCfg(Go1RoughTerrainCfg):
     envs/base/history.py).  No privileged row: the critic reads the same 475 entries."""
     class history(Go1RoughTerrainCfg.history):
         frames = 5
+
+
+class Go1RoughActRandCfg(Go1RoughTerrainCfg):
+    """go1_rough with the actuator randomised per env (no reference counterpart): motor strength, PD
+    gains and an action latency of 0 .. 4 substeps (envs/base/actuator_rand.py).  No privileged row and
+    no history: the policy has to be robust to what it cannot observe."""
+    class actuator_rand(Go1RoughTerrainCfg.actuator_rand):
+        randomize_motor_strength = True
+        randomize_kp = True
+        randomize_kd = True
+        randomize_lag = True
 
 
 class Go1RoughAsymHistCfg(Go1RoughAsymCfg):

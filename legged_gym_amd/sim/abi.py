@@ -164,6 +164,10 @@ class LgxObsHistoryDesc(C.Structure):   # lgx_obs_history_desc (layout: envs/bas
     _fields_ = [("frames", i32), ("frame_width", i32), ("width", i32)]
 
 
+class LgxActuatorRandDesc(C.Structure):   # lgx_actuator_rand_desc (the draws: envs/base/actuator_rand.py)
+    _fields_ = [("kp_scale", C.c_void_p), ("kd_scale", C.c_void_p), ("lag", C.c_void_p)]
+
+
 PPO_MAX_ACTIONS = 16
 MAX_REDUCE_JOBS = 16
 EPISODE_RING_MAX = 4096   # LGX_EPISODE_RING_MAX: largest ring of lgx_episode_stats_step
@@ -215,6 +219,7 @@ def declare(lib, prefix="lgx"):
             "rebind_privileged_obs": (C.c_int, [vp, vp]),
             "bind_obs_history": (C.c_int, [vp, vp, vp, C.POINTER(LgxObsHistoryDesc)]),
             "rebind_obs_history": (C.c_int, [vp, vp, vp]),
+            "bind_actuator_rand": (C.c_int, [vp, C.POINTER(LgxActuatorRandDesc)]),
             "sim_buffer": (C.c_int, [vp, i32, C.POINTER(vp), C.POINTER(i64), C.POINTER(i32), C.POINTER(i32)]),
             "ppo_gather_rows": (C.c_int, [vp, vp, vp, i64, i32, vp]),
             "ppo_act": (C.c_int, [C.POINTER(LgxPpoActArgs), vp]),
@@ -276,7 +281,7 @@ def declare(lib, prefix="lgx"):
 
 
 EXPORTED = ["lgx_last_error", "lgx_version", "lgx_physics_lane_split", "lgx_trimesh_build", "lgx_struct_sizes", "lgx_scratch_floats", "lgx_sim_create",
-            "lgx_sim_destroy", "lgx_step", "lgx_simulate", "lgx_post_physics", "lgx_post_physics_fused", "lgx_reset_idx", "lgx_set_draws", "lgx_rebind_obs", "lgx_rebind_extras", "lgx_bind_privileged_obs", "lgx_rebind_privileged_obs", "lgx_bind_obs_history", "lgx_rebind_obs_history", "lgx_sim_buffer", "lgx_step_from", "lgx_drive_inputs", "lgx_ground_contact", "lgx_sync_aux",
+            "lgx_sim_destroy", "lgx_step", "lgx_simulate", "lgx_post_physics", "lgx_post_physics_fused", "lgx_reset_idx", "lgx_set_draws", "lgx_rebind_obs", "lgx_rebind_extras", "lgx_bind_privileged_obs", "lgx_rebind_privileged_obs", "lgx_bind_obs_history", "lgx_rebind_obs_history", "lgx_bind_actuator_rand", "lgx_sim_buffer", "lgx_step_from", "lgx_drive_inputs", "lgx_ground_contact", "lgx_sync_aux",
             "lgx_actuator_mlp", "lgx_actuator_lstm", "lgx_mlp_forward", "lgx_gae", "lgx_gae_norm_scratch", "lgx_gae_norm", "lgx_gae_parts", "lgx_adv_norm",
             "lgx_profile_enable", "lgx_profile_collect", "lgx_mlp_forward_batch",
             "lgx_ppo_gather_rows", "lgx_bias_act", "lgx_ppo_loss_partials_floats", "lgx_ppo_loss", "lgx_ppo_adapt_lr",
