@@ -601,6 +601,54 @@ int lgx_adv_norm(float* advantages, int64_t n, const double* parts, int32_t npar
 int lgx_episode_stats_step(const float* rew, const uint8_t* dones, int64_t num_envs, float* cur_sum, float* cur_len,
                            float* ring_sum, float* ring_len, int32_t capacity, int64_t* count, void* stream);
 
+/* Empirical observation normalisation (rsl_rl 2.x EmpiricalNormalization): a running mean and
+ * population standard deviation per observation column, updated from each env step's batch and
+ * applied to it before the policy and the critic read it.
+ *
+ * A normaliser of width D (1 <= D <= LGX_MAX_PRIV_OBS) has a float64 state of 1 + 2 D doubles:
+ * [0] n (integer-valued), [1 .. D] mean, [1 + D .. 2 D] M2 (sum of squared deviations); all zeros
+ * when empty.  A training step on x [rows, D] is two launches:
+ *   lgx_obs_norm_partials  cuts the rows into consecutive blocks of LGX_OBS_NORM_ROWS (the last may
+ *     be shorter) and writes block b's (n_b, mean_b[D], M2_b[D]), in the state's layout, to
+ *     parts[b * (1 + 2 D) ...]: per column the float64 sum of the block's rows in ascending order,
+ *     mean_b = sum / n_b, then M2_b = sum of (x - mean_b)^2 in ascending order;
+ *   lgx_obs_norm_apply     with update != 0 folds parts[0 .. nparts) into state_in in ascending
+ *     order (n = n_a + n_b, d = mean_b - mean_a, w = n_b / n, mean = mean_a + d w,
+ *     M2 = M2_a + M2_b + d^2 n_a w), writes the result to state_out (!= state_in, which the launch
+ *     only reads), and from the folded values writes
+ *         y = (x - (float)mean) * (float)(1 / (sqrt(M2 / n) + eps)).
+ *     nparts is the caller's count and may exceed ceil(rows / LGX_OBS_NORM_ROWS): a data-parallel
+ *     run passes every rank's partials, gathered in rank order, and every rank then holds the same
+ *     state.  update == 0 (a frozen call) normalises with state_in as it is (n == 0: mean 0, std 1)
+ *     and reads neither parts nor state_out.
+ * Both take up to LGX_OBS_NORM_MAX_JOBS jobs in one launch.  No atomics and one writer per output:
+ * the same partials in the same order give the same bits, whichever launches computed them, so
+ * partials of rows [0, k R) and [k R, rows) written by two calls equal one call's.
+ * y may be x itself (each element is read and then written by the same thread, after the partials
+ * launch has finished); they must not overlap otherwise.  parts, the states, x and y are device
+ * pointers; the jobs array is host memory.
+ * LGX_EINVAL (message in lgx_last_error, nothing launched) for null jobs or a null pointer a call
+ * uses, njobs outside [1, LGX_OBS_NORM_MAX_JOBS], rows < 1, width outside [1, LGX_MAX_PRIV_OBS],
+ * state_out == state_in, or (update) nparts < ceil(rows / LGX_OBS_NORM_ROWS). */
+#define LGX_OBS_NORM_ROWS 64       /* R: rows per partial; part of the result's definition */
+#define LGX_OBS_NORM_MAX_JOBS 2
+typedef struct lgx_obs_norm_job {
+  const float* x;          /* [rows, width] */
+  float* y;                /* [rows, width] (apply) */
+  int64_t rows;
+  int32_t width;
+  int32_t update;          /* apply: fold parts into the state first */
+  double* parts;           /* partials: written; apply (update): nparts entries read */
+  int64_t nparts;          /* apply (update) */
+  const double* state_in;  /* apply */
+  double* state_out;       /* apply (update) */
+  double eps;              /* apply */
+} lgx_obs_norm_job;
+int32_t lgx_obs_norm_rows_per_part(void);                    /* LGX_OBS_NORM_ROWS of this library */
+int64_t lgx_obs_norm_part_doubles(int64_t rows, int32_t width);   /* doubles lgx_obs_norm_partials writes */
+int lgx_obs_norm_partials(const lgx_obs_norm_job* jobs, int32_t njobs, void* stream);
+int lgx_obs_norm_apply(const lgx_obs_norm_job* jobs, int32_t njobs, void* stream);
+
 /* ---- PPO update (rsl_rl PPO.update, legged_robot_config.py:226-239): the non-GEMM work of a
  * minibatch step.  Activations are net-major [2 (actor, critic), M, H]; the GEMMs between
  * these calls are library GEMMs issued by the host.  All pointers are device pointers. */

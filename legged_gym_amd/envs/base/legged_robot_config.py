@@ -255,3 +255,7 @@ class LeggedRobotCfgPPO(BaseConfig):  # ref :218-255
         load_run = 'Dec21_16-36-59_'
         checkpoint = -1
         resume_path = None
+        # rsl_rl 2.x: a running mean / std per observation column in front of the actor and the
+        # critic (rl/normalizer.py); `until`: stop updating once that many rows have been counted
+        empirical_normalization = False
+        empirical_normalization_until = None

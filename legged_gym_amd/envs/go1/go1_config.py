@@ -70,6 +70,12 @@ class Go1RoughCfgPPO(LeggedRobotCfgPPO):
         experiment_name = 'rough_go1'
 
 
+class Go1RoughNormCfgPPO(Go1RoughCfgPPO):
+    """Go1RoughCfgPPO with empirical observation normalisation in front of the actor and the critic."""
+    class runner(Go1RoughCfgPPO.runner):
+        empirical_normalization = True
+
+
 class Go1FlatBenchCfg(Go1RoughCfg):
     """BASELINE config C2: flat, PD actuator, no domain randomisation."""
     class control(Go1RoughCfg.control):

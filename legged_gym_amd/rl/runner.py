@@ -7,6 +7,14 @@ optimizer_state_dict, iter, infos} saved every `save_interval` iterations as mod
 Timing: `collection_time` (act + env.step + storage) and `learn_time` (GAE + update) per
 iteration, fps = num_steps_per_env * num_envs / (collection + learn), as rsl_rl logs it;
 `last_iteration_stats` keeps them for bench.py.
+
+`runner.empirical_normalization = True` (rsl_rl 2.x's key; off by default, and a dict without it is
+off) puts an EmpiricalNormalization (rl/normalizer.py) in front of the actor and the critic:
+`obs_normalizer` (env.num_obs wide) and `critic_obs_normalizer` (num_privileged_obs wide; the same
+object when the env has no privileged row).  learn() normalises each step's rows right after
+env.step, with an update; the storage, the returns and the update then see normalised rows.  The
+checkpoint gains `obs_norm_state_dict` (and `critic_obs_norm_state_dict` for a separate critic
+normaliser), and load() refuses a checkpoint from the other side of the flag.
 """
 import os
 import statistics
@@ -16,6 +24,7 @@ import torch
 
 from .actor_critic import ActorCritic, ActorCriticRecurrent  # noqa: F401  (resolved by name from the cfg)
 from .episode_stats import EpisodeStats
+from .normalizer import EmpiricalNormalization, normalize_many
 from .ppo import PPO  # noqa: F401
 
 
@@ -36,6 +45,13 @@ class OnPolicyRunner:
         self.save_interval = self.cfg["save_interval"]
         self.alg.init_storage(self.env.num_envs, self.num_steps_per_env, [self.env.num_obs],
                               [self.env.num_privileged_obs], [self.env.num_actions])
+        self.obs_normalizer = self.critic_obs_normalizer = None
+        if self.cfg.get("empirical_normalization", False):
+            until = self.cfg.get("empirical_normalization_until")
+            self.obs_normalizer = EmpiricalNormalization(self.env.num_obs, until=until, device=self.device)
+            self.critic_obs_normalizer = self.obs_normalizer
+            if self.env.num_privileged_obs is not None:
+                self.critic_obs_normalizer = EmpiricalNormalization(num_critic_obs, until=until, device=self.device)
         self.log_dir = log_dir
         self.writer = None
         self.tot_timesteps = 0
@@ -53,6 +69,17 @@ class OnPolicyRunner:
                 self.writer = False
         return self.writer or None
 
+    def _normalize(self, obs, critic_obs, update=None):
+        """(obs, critic_obs) through the normalisers (both in the same launches; one shared
+        normaliser: applied once, the one result for actor and critic); as they are with the flag off."""
+        nz, cz = self.obs_normalizer, self.critic_obs_normalizer
+        if nz is None:
+            return obs, critic_obs
+        if cz is nz:
+            y = nz(obs, update)
+            return y, y
+        return tuple(normalize_many([nz, cz], [obs, critic_obs], update))
+
     def learn(self, num_learning_iterations, init_at_random_ep_len=False):
         if init_at_random_ep_len:
             self.env.episode_length_buf = torch.randint_like(self.env.episode_length_buf,
@@ -61,6 +88,11 @@ class OnPolicyRunner:
         privileged_obs = self.env.get_privileged_observations()
         critic_obs = privileged_obs if privileged_obs is not None else obs
         obs, critic_obs = obs.to(self.device), critic_obs.to(self.device)
+        normalizing = self.obs_normalizer is not None
+        if normalizing:
+            # counted only by an empty normaliser: otherwise this row was the last one of the
+            # previous learn() (or of the run the checkpoint came from) and is in the statistics
+            obs, critic_obs = self._normalize(obs, critic_obs, update=self.obs_normalizer.count == 0)
         self.alg.actor_critic.train()
         ep_infos = []
         # Phase times on CUDA come from stream events read after update(), whose statistics readback
@@ -106,6 +138,8 @@ class OnPolicyRunner:
                         obs, privileged_obs, rewards, dones, infos = self.env.step(actions)
                         critic_obs = privileged_obs if privileged_obs is not None else obs
                         obs, critic_obs = obs.to(self.device), critic_obs.to(self.device)
+                        if normalizing:
+                            obs, critic_obs = self._normalize(obs, critic_obs)
                         rewards, dones = rewards.to(self.device), dones.to(self.device)
                         self.alg.process_env_step(rewards, dones, infos)
                         if logged:
@@ -253,12 +287,30 @@ class OnPolicyRunner:
         print(s)
 
     def save(self, path, infos=None):
-        torch.save({"model_state_dict": self.alg.actor_critic.state_dict(),
-                    "optimizer_state_dict": self.alg.optimizer.state_dict(),
-                    "iter": self.current_learning_iteration, "infos": infos}, path)
+        d = {"model_state_dict": self.alg.actor_critic.state_dict(),
+             "optimizer_state_dict": self.alg.optimizer.state_dict(),
+             "iter": self.current_learning_iteration, "infos": infos}
+        if self.obs_normalizer is not None:
+            d["obs_norm_state_dict"] = self.obs_normalizer.state_dict()
+            if self.critic_obs_normalizer is not self.obs_normalizer:
+                d["critic_obs_norm_state_dict"] = self.critic_obs_normalizer.state_dict()
+        torch.save(d, path)
 
     def load(self, path, load_optimizer=True):
         d = torch.load(path, map_location=self.device, weights_only=True)
+        # a policy must not run on the wrong side of its normaliser
+        has = "obs_norm_state_dict" in d or "critic_obs_norm_state_dict" in d
+        if self.obs_normalizer is None and has:
+            raise ValueError(f"{path} holds observation-normaliser statistics, but this runner has "
+                             "runner.empirical_normalization off")
+        if self.obs_normalizer is not None:
+            separate = self.critic_obs_normalizer is not self.obs_normalizer
+            if "obs_norm_state_dict" not in d or (separate and "critic_obs_norm_state_dict" not in d):
+                raise ValueError(f"{path} holds no observation-normaliser statistics, but this runner has "
+                                 "runner.empirical_normalization on")
+            self.obs_normalizer.load_state_dict(d["obs_norm_state_dict"])
+            if separate:
+                self.critic_obs_normalizer.load_state_dict(d["critic_obs_norm_state_dict"])
         self.alg.actor_critic.load_state_dict(d["model_state_dict"])
         if hasattr(self.alg.actor_critic, "invalidate_fused"):
             self.alg.actor_critic.invalidate_fused()
@@ -275,7 +327,14 @@ class OnPolicyRunner:
         self.alg.actor_critic.eval()
         if device is not None:
             self.alg.actor_critic.to(device)
-        return self.alg.actor_critic.act_inference
+        act_inference = self.alg.actor_critic.act_inference
+        if self.obs_normalizer is None:
+            return act_inference
+        nz = self.obs_normalizer if device is None else self.obs_normalizer.to(device)
+
+        def policy(obs):   # the frozen normaliser, then the actor: the statistics stay as they are
+            return act_inference(nz(obs, update=False))
+        return policy
 
     def close(self):
         """Release the update's collective resources (the lgx RCCL communicator of

@@ -43,7 +43,7 @@ def play(args, steps=1000):
     policy = ppo_runner.get_inference_policy(device=env.device)
     if EXPORT_POLICY:
         path = os.path.join(LEGGED_GYM_ROOT_DIR, "logs", train_cfg.runner.experiment_name, "exported", "policies")
-        export_policy_as_jit(ppo_runner.alg.actor_critic, path)
+        export_policy_as_jit(ppo_runner.alg.actor_critic, path, normalizer=ppo_runner.obs_normalizer)
         print("Exported policy as jit script to: ", path)
     from legged_gym_amd.utils.logger import Logger
     logger = Logger(env.dt)

@@ -168,6 +168,14 @@ class LgxActuatorRandDesc(C.Structure):   # lgx_actuator_rand_desc (the draws: e
     _fields_ = [("kp_scale", C.c_void_p), ("kd_scale", C.c_void_p), ("lag", C.c_void_p)]
 
 
+class LgxObsNormJob(C.Structure):   # lgx_obs_norm_job (rl/normalizer.py)
+    _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("rows", i64), ("width", i32), ("update", i32),
+                ("parts", C.c_void_p), ("nparts", i64), ("state_in", C.c_void_p), ("state_out", C.c_void_p),
+                ("eps", C.c_double)]
+
+
+OBS_NORM_ROWS = 64        # LGX_OBS_NORM_ROWS (checked against lgx_obs_norm_rows_per_part at first use)
+OBS_NORM_MAX_JOBS = 2     # LGX_OBS_NORM_MAX_JOBS
 PPO_MAX_ACTIONS = 16
 MAX_REDUCE_JOBS = 16
 EPISODE_RING_MAX = 4096   # LGX_EPISODE_RING_MAX: largest ring of lgx_episode_stats_step
@@ -272,6 +280,10 @@ def declare(lib, prefix="lgx"):
             "comm_destroy": (C.c_int, [vp]),
             "allreduce_grads": (C.c_int, [vp, vp, C.c_size_t, i32, vp]),
             "episode_stats_step": (C.c_int, [vp, vp, i64, vp, vp, vp, vp, i32, vp, vp]),
+            "obs_norm_rows_per_part": (i32, []),
+            "obs_norm_part_doubles": (i64, [i64, i32]),
+            "obs_norm_partials": (C.c_int, [C.POINTER(LgxObsNormJob), i32, vp]),
+            "obs_norm_apply": (C.c_int, [C.POINTER(LgxObsNormJob), i32, vp]),
         })
     for name, (res, args) in sigs.items():
         fn = getattr(lib, f"{prefix}_{name}")
@@ -293,7 +305,8 @@ EXPORTED = ["lgx_last_error", "lgx_version", "lgx_physics_lane_split", "lgx_trim
             "lgx_event_create", "lgx_event_destroy", "lgx_event_record", "lgx_stream_wait_event",
             "lgx_launch_bind_event", "lgx_launch_bind_pending",
             "lgx_comm_unique_id", "lgx_comm_create", "lgx_comm_destroy", "lgx_allreduce_grads",
-            "lgx_episode_stats_step"]
+            "lgx_episode_stats_step",
+            "lgx_obs_norm_rows_per_part", "lgx_obs_norm_part_doubles", "lgx_obs_norm_partials", "lgx_obs_norm_apply"]
 
 
 def check_layout(sizes_fn, n=12):

@@ -188,15 +188,38 @@ def _plain_actor(actor):
     return nn.Sequential(*layers)
 
 
-def export_policy_as_jit(actor_critic, path):
+def _frozen_normalization_cls():
+    import torch
+
+    class FrozenNormalization(torch.nn.Module):
+        """An EmpiricalNormalization (rl/normalizer.py) as it is now, frozen: float32 `mean` / `inv`
+        buffers and y = (x - mean) * inv, nothing of this package."""
+
+        def __init__(self, normalizer):
+            super().__init__()
+            self.register_buffer("mean", normalizer.mean.detach().cpu().clone())
+            self.register_buffer("inv", normalizer.inv().detach().cpu().clone())
+
+        def forward(self, x):
+            return (x - self.mean) * self.inv
+
+    return FrozenNormalization
+
+
+def export_policy_as_jit(actor_critic, path, normalizer=None):
     """helpers.py:180-190: TorchScript export of the actor MLP as policy_1.pt, or, for a recurrent
-    policy (one with `memory_a`), of memory + actor as policy_lstm_1.pt (PolicyExporterLSTM)."""
+    policy (one with `memory_a`), of memory + actor as policy_lstm_1.pt (PolicyExporterLSTM).
+    normalizer: the runner's obs_normalizer; its frozen normalisation is exported in front of the
+    policy, which then takes raw observations."""
     import torch
     if hasattr(actor_critic, "memory_a"):
-        PolicyExporterLSTM(actor_critic).export(path)
+        PolicyExporterLSTM(actor_critic, normalizer).export(path)
         return
     os.makedirs(path, exist_ok=True)
-    torch.jit.script(_plain_actor(actor_critic.actor)).save(os.path.join(path, "policy_1.pt"))
+    actor = _plain_actor(actor_critic.actor)
+    if normalizer is not None:
+        actor = torch.nn.Sequential(_frozen_normalization_cls()(normalizer), actor)
+    torch.jit.script(actor).save(os.path.join(path, "policy_1.pt"))
 
 
 def _policy_exporter_lstm_cls():
@@ -206,16 +229,18 @@ def _policy_exporter_lstm_cls():
         """helpers.py:193-219: the actor's LSTM + MLP as one TorchScript module that carries its
         (layers, 1, hidden) h / c state across calls; reset_memory() zeroes it."""
 
-        def __init__(self, actor_critic):
+        def __init__(self, actor_critic, normalizer=None):
             super().__init__()
             self.actor = _plain_actor(actor_critic.actor)
+            self.normalizer = (torch.nn.Identity() if normalizer is None
+                               else _frozen_normalization_cls()(normalizer))
             self.is_recurrent = actor_critic.is_recurrent
             self.memory = copy.deepcopy(actor_critic.memory_a.rnn).cpu()
             self.register_buffer("hidden_state", torch.zeros(self.memory.num_layers, 1, self.memory.hidden_size))
             self.register_buffer("cell_state", torch.zeros(self.memory.num_layers, 1, self.memory.hidden_size))
 
         def forward(self, x):
-            out, (h, c) = self.memory(x.unsqueeze(0), (self.hidden_state, self.cell_state))
+            out, (h, c) = self.memory(self.normalizer(x).unsqueeze(0), (self.hidden_state, self.cell_state))
             self.hidden_state[:] = h
             self.cell_state[:] = c
             return self.actor(out.squeeze(0))
@@ -233,7 +258,7 @@ def _policy_exporter_lstm_cls():
     return PolicyExporterLSTM
 
 
-def PolicyExporterLSTM(actor_critic):  # noqa: N802  (the reference's class name; torch imported lazily)
-    return _policy_exporter_lstm_cls()(actor_critic)
+def PolicyExporterLSTM(actor_critic, normalizer=None):  # noqa: N802  (the reference's class name; torch imported lazily)
+    return _policy_exporter_lstm_cls()(actor_critic, normalizer)
 
 

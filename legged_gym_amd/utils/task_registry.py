@@ -1,7 +1,8 @@
 """Task registry: name -> (env class, env cfg, train cfg); env and runner factories.
 
 Same API and behaviour as legged_gym/utils/task_registry.py:46-171 (register / get_task_class /
-get_cfgs / make_env / make_alg_runner, log-dir layout and resume).  The runner is the in-repo
+get_cfgs / make_env / make_alg_runner, log-dir layout and resume), plus `register_variant`: a
+registered task under a second name with another train cfg.  The runner is the in-repo
 rsl_rl-compatible `OnPolicyRunner` (legged_gym_amd.rl) unless `rsl_rl` is importable and
 `LGX_USE_RSL_RL=1` is set, in which case the upstream runner drops in unchanged.
 """
@@ -31,25 +32,38 @@ class TaskRegistry:
         self.task_classes = {}
         self.env_cfgs = {}
         self.train_cfgs = {}
+        self.variants = {}   # name -> the registered task it trains differently (register_variant)
 
     def register(self, name: str, task_class, env_cfg: "LeggedRobotCfg", train_cfg: "LeggedRobotCfgPPO"):
         self.task_classes[name] = task_class
         self.env_cfgs[name] = env_cfg
         self.train_cfgs[name] = train_cfg
 
+    def register_variant(self, name: str, base: str, train_cfg: "LeggedRobotCfgPPO"):
+        """`base` under a second name with a train cfg of its own: the same env class and the same
+        env cfg object, so `task_classes` / `env_cfgs` keep one entry per env (no reference
+        counterpart; `--task name` selects it like any task)."""
+        if base not in self.task_classes:
+            raise ValueError(f"Task with name: {base} was not registered")
+        self.variants[name] = base
+        self.train_cfgs[name] = train_cfg
+
+    def _env_name(self, name):
+        return self.variants.get(name, name)
+
     def get_task_class(self, name: str):
-        return self.task_classes[name]
+        return self.task_classes[self._env_name(name)]
 
     def get_cfgs(self, name) -> Tuple["LeggedRobotCfg", "LeggedRobotCfgPPO"]:
         train_cfg = self.train_cfgs[name]
-        env_cfg = self.env_cfgs[name]
+        env_cfg = self.env_cfgs[self._env_name(name)]
         env_cfg.seed = train_cfg.seed  # task_registry.py:63-64
         return env_cfg, train_cfg
 
     def make_env(self, name, args=None, env_cfg=None):
         if args is None:
             args = get_args()
-        if name not in self.task_classes:
+        if self._env_name(name) not in self.task_classes:
             raise ValueError(f"Task with name: {name} was not registered")
         task_class = self.get_task_class(name)
         if env_cfg is None:

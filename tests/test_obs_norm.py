@@ -1,0 +1,417 @@
+"""CPU: the empirical observation normaliser (legged_gym_amd/rl/normalizer.py) on its torch float64
+path, against tests/obs_norm_ref.py; the C-ABI's argument validation (no launch, so no GPU); the
+runner, the export and the data-parallel path (gloo, world 2).
+
+The first test shows that the torch restatement alone stays inside the oracle's bounds on the
+inputs the GPU tests use: the bounds are reachable before the kernels are asked to meet them.
+"""
+import ctypes as C
+import os
+import re
+import socket
+
+import numpy as np
+import pytest
+import torch
+import torch.multiprocessing as mp
+
+import obs_norm_ref as ref
+from legged_gym_amd.rl.normalizer import EmpiricalNormalization, normalize_many, rows_per_part
+from legged_gym_amd.sim import abi
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+R = rows_per_part()
+SHAPES = [(rows, w) for w in ref.WIDTHS for rows in ref.row_counts(R)] + [(4096, 253)]
+NEW_SYMBOLS = ["lgx_obs_norm_rows_per_part", "lgx_obs_norm_part_doubles", "lgx_obs_norm_partials",
+               "lgx_obs_norm_apply"]
+
+
+def state_of(nz):
+    d = nz.state_dict()
+    return int(d["count"]), d["mean"].numpy(), d["m2"].numpy()
+
+
+def same_state(a, b):
+    da, db = a.state_dict(), b.state_dict()
+    return all(torch.equal(da[k], db[k]) for k in ("count", "mean", "m2"))
+
+
+def run_calls(nz, batches, device="cpu"):
+    return [nz(torch.from_numpy(b).to(device)) for b in batches]
+
+
+# ---------------------------------------------------------------------- semantics
+@pytest.mark.parametrize("rows,width", SHAPES)
+def test_torch_restatement_meets_the_oracle_bounds(rows, width):
+    batches = ref.make_batches(rows, width)
+    nz = EmpiricalNormalization(width, device="cpu")
+    for k, b in enumerate(batches):
+        y = nz(torch.from_numpy(b))
+        assert y.dtype == torch.float32 and y.shape == b.shape
+        ref.check_state(*state_of(nz), batches[:k + 1], what=f"cpu {rows}x{width} call {k}")
+        ref.check_y(y.numpy(), b, batches[:k + 1], what=f"cpu {rows}x{width} call {k}")
+    assert nz.count == 3 * rows
+    torch.testing.assert_close(nz.mean.double(), nz.state_dict()["mean"], rtol=2 ** -23, atol=0)
+
+
+def test_columns_that_catch_wrong_arithmetic():
+    """What the constant and the offset column are in the inputs for, stated directly."""
+    batches = ref.make_batches(3 * R + 17, 48)
+    nz = EmpiricalNormalization(48, device="cpu")
+    ys = run_calls(nz, batches)
+    d = nz.state_dict()
+    assert d["m2"][1] == 0 and (ys[-1][:, 1] == 0).all()             # constant: variance exactly 0
+    assert float(nz.inv()[1]) == pytest.approx(1 / ref.EPS, rel=1e-6)
+    std0 = float(torch.sqrt(d["m2"][0] / d["count"]))                # mean 100, std 1e-3
+    assert std0 == pytest.approx(1e-3, rel=0.1)
+    # an f32 sum / sum-of-squares accumulation loses that column entirely
+    x = torch.from_numpy(np.concatenate(batches))[:, 0]
+    var_f32 = float((x * x).mean() - x.mean() ** 2)
+    assert abs(var_f32 - std0 ** 2) > 10 * std0 ** 2
+
+
+def test_empty_frozen_call_is_mean_0_std_1():
+    nz = EmpiricalNormalization(5, eps=0.25, device="cpu")
+    x = torch.randn(7, 5)
+    y = nz(x, update=False)
+    assert torch.equal(y, x * torch.tensor(1 / 1.25, dtype=torch.float32)) and nz.count == 0
+    assert torch.equal(nz.std, torch.ones(5)) and torch.equal(nz.mean, torch.zeros(5))
+
+
+def test_rejects_what_it_does_not_take():
+    with pytest.raises(ValueError):
+        EmpiricalNormalization(0)
+    with pytest.raises(ValueError):
+        EmpiricalNormalization(abi.MAX_PRIV_OBS + 1)
+    nz = EmpiricalNormalization(4)
+    for bad in (torch.zeros(3, 5), torch.zeros(0, 4), torch.zeros(3, 4, dtype=torch.float64), torch.zeros(4)):
+        with pytest.raises(ValueError):
+            nz(bad)
+    with pytest.raises(ValueError):
+        normalize_many([nz, nz], [torch.zeros(1, 4)] * 2)
+
+
+# ---------------------------------------------------------------------- bitwise properties
+def test_two_runs_agree_bitwise():
+    batches = ref.make_batches(3 * R + 17, 253)
+    a, b = EmpiricalNormalization(253), EmpiricalNormalization(253)
+    ya, yb = run_calls(a, batches), run_calls(b, batches)
+    assert same_state(a, b) and all(torch.equal(p, q) for p, q in zip(ya, yb))
+
+
+def test_split_equivalence():
+    """Partials of rows [0, R) and [R, 4R) computed apart, concatenated and applied == one call."""
+    (b,) = ref.make_batches(4 * R, 253, calls=1)
+    x = torch.from_numpy(b)
+    whole, split = EmpiricalNormalization(253), EmpiricalNormalization(253)
+    y = whole(x)
+    parts = torch.cat([split.partials(x[:R]), split.partials(x[R:])])
+    y2 = split.apply(x, parts)
+    assert torch.equal(y, y2) and same_state(whole, split) and split.count == 4 * R
+
+
+def test_frozen_call_and_until():
+    batches = ref.make_batches(R + 1, 48, calls=4)
+    nz = EmpiricalNormalization(48, until=2 * (R + 1))
+    run_calls(nz, batches[:1])
+    before = nz.state_dict()
+    y = nz(torch.from_numpy(batches[1]), update=False)
+    after = nz.state_dict()
+    assert all(torch.equal(before[k], after[k]) for k in before), "a frozen call writes nothing"
+    ref.check_y(y.numpy(), batches[1], batches[:1], what="frozen")
+    run_calls(nz, batches[1:2])
+    assert nz.count == 2 * (R + 1) and nz.frozen()          # n first reaches `until` here ...
+    at = nz.state_dict()
+    y = nz(torch.from_numpy(batches[2]))                     # ... so this training call is frozen
+    assert nz.count == 2 * (R + 1) and all(torch.equal(at[k], nz.state_dict()[k]) for k in at)
+    ref.check_y(y.numpy(), batches[2], batches[:2], what="until")
+    free = EmpiricalNormalization(48, until=None)
+    run_calls(free, batches)
+    assert free.count == 4 * (R + 1)
+
+
+def test_state_dict_round_trip_continues_bitwise():
+    batches = ref.make_batches(3 * R + 17, 257, calls=4)
+    straight, first = EmpiricalNormalization(257), EmpiricalNormalization(257)
+    ys = run_calls(straight, batches)
+    run_calls(first, batches[:2])
+    d = first.state_dict()
+    assert d["count"].dtype == torch.int64 and d["mean"].dtype == d["m2"].dtype == torch.float64
+    assert set(d) == {"count", "mean", "m2"}
+    resumed = EmpiricalNormalization(257)
+    resumed.load_state_dict(d)
+    yr = run_calls(resumed, batches[2:])
+    assert same_state(straight, resumed) and all(torch.equal(p, q) for p, q in zip(ys[2:], yr))
+    with pytest.raises(ValueError):
+        EmpiricalNormalization(48).load_state_dict(d)
+
+
+# ---------------------------------------------------------------------- the C ABI
+def test_header_bindings_and_library_hold_the_entry_points():
+    txt = open(os.path.join(ROOT, "include", "lgx.h")).read()
+    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    import torch  # noqa: F401  (HIP runtime first)
+    lib = C.CDLL(os.path.join(ROOT, "legged_gym_amd", "liblgx.so"))
+    for name in NEW_SYMBOLS:
+        assert re.search(r"\b%s\s*\(" % name, txt), name
+        assert name in abi.EXPORTED and hasattr(lib, name), name
+    abi.declare(lib)
+    assert lib.lgx_obs_norm_rows_per_part() == abi.OBS_NORM_ROWS == R
+    assert re.search(r"#define\s+LGX_OBS_NORM_ROWS\s+%d\b" % R, txt)
+    assert re.search(r"#define\s+LGX_OBS_NORM_MAX_JOBS\s+%d\b" % abi.OBS_NORM_MAX_JOBS, txt)
+    assert lib.lgx_obs_norm_part_doubles(3 * R + 17, 253) == 4 * (1 + 2 * 253)
+
+
+def good_job(update=1, rows=3 * R + 17, width=253):
+    j = abi.LgxObsNormJob()
+    j.x, j.y, j.parts, j.state_in, j.state_out = 0x1000, 0x2000, 0x3000, 0x4000, 0x5000
+    j.rows, j.width, j.update, j.nparts, j.eps = rows, width, update, -(-rows // R), 1e-2
+    return j
+
+
+@pytest.mark.parametrize("entry,field,value,msg", [
+    ("partials", "x", None, "null"), ("partials", "parts", None, "null"),
+    ("apply", "x", None, "null"), ("apply", "y", None, "null"), ("apply", "state_in", None, "null"),
+    ("apply", "parts", None, "null"), ("apply", "state_out", None, "null"),
+    ("apply", "state_out", 0x4000, "state_in"),
+    ("partials", "rows", 0, "rows"), ("apply", "rows", -3, "rows"),
+    ("partials", "width", 0, "width"), ("apply", "width", abi.MAX_PRIV_OBS + 1, "width"),
+    ("apply", "nparts", 3, "nparts"), ("apply", "nparts", 0, "nparts"),
+])
+def test_entry_points_validate_before_any_launch(entry, field, value, msg):
+    """Every LGX_EINVAL case returns the code and a message.  The checks precede any device call
+    (the pointers here are not device memory), so this runs without a GPU."""
+    import torch  # noqa: F401
+    lib = abi.declare(C.CDLL(os.path.join(ROOT, "legged_gym_amd", "liblgx.so")))
+    fn = getattr(lib, f"lgx_obs_norm_{entry}")
+    for slot in range(2):                       # the bad job first, and behind a good one
+        jobs = (abi.LgxObsNormJob * 2)(good_job(), good_job())
+        setattr(jobs[slot], field, value)
+        assert fn(jobs, 2, None) == -1, (entry, field, slot)
+        err = lib.lgx_last_error().decode()
+        assert msg in err and f"lgx_obs_norm_{entry}" in err, err
+
+
+def test_entry_points_reject_bad_job_counts():
+    import torch  # noqa: F401
+    lib = abi.declare(C.CDLL(os.path.join(ROOT, "legged_gym_amd", "liblgx.so")))
+    jobs = (abi.LgxObsNormJob * 3)(good_job(), good_job(), good_job())
+    for fn in (lib.lgx_obs_norm_partials, lib.lgx_obs_norm_apply):
+        for n in (3, 0, -1):
+            assert fn(jobs, n, None) == -1 and "njobs" in lib.lgx_last_error().decode()
+        assert fn(None, 1, None) == -1 and "null jobs" in lib.lgx_last_error().decode()
+    # a frozen apply needs neither partials nor an output state
+    j = good_job(update=0)
+    j.parts = j.state_out = None
+    j.x = None
+    assert lib.lgx_obs_norm_apply((abi.LgxObsNormJob * 1)(j), 1, None) == -1
+    assert "null x" in lib.lgx_last_error().decode()
+
+
+# ---------------------------------------------------------------------- runner (CPU path)
+def make_runner(tmp_path=None, norm=True, until=None, recurrent=False, steps=4, num_envs=8):
+    from oracle_backend import make_env
+    from legged_gym_amd.envs.go1.go1_config import Go1RoughCfgPPO
+    from legged_gym_amd.rl.runner import OnPolicyRunner
+    from legged_gym_amd.utils.helpers import class_to_dict
+    env = make_env("go1_flat_bench", num_envs=num_envs, device="cpu", backend="oracle")
+    cfg = class_to_dict(Go1RoughCfgPPO())
+    cfg["runner"]["num_steps_per_env"] = steps
+    if norm:
+        cfg["runner"]["empirical_normalization"] = True
+        cfg["runner"]["empirical_normalization_until"] = until
+    else:   # an rsl_rl 1.x dict: the keys are absent
+        del cfg["runner"]["empirical_normalization"], cfg["runner"]["empirical_normalization_until"]
+    if recurrent:
+        cfg["runner"]["policy_class_name"] = "ActorCriticRecurrent"
+        cfg["policy"].update(rnn_type="lstm", rnn_hidden_size=32, rnn_num_layers=1, actor_hidden_dims=[32, 16],
+                             critic_hidden_dims=[32, 16])
+        cfg["algorithm"]["num_mini_batches"] = 2
+    torch.manual_seed(0)
+    return OnPolicyRunner(env, cfg, None if tmp_path is None else str(tmp_path), device="cpu"), env, cfg
+
+
+def test_config_has_the_keys_off_by_default():
+    from legged_gym_amd.envs.base.legged_robot_config import LeggedRobotCfgPPO
+    import legged_gym_amd.envs  # noqa: F401
+    from legged_gym_amd.utils.task_registry import task_registry
+    assert LeggedRobotCfgPPO.runner.empirical_normalization is False
+    assert LeggedRobotCfgPPO.runner.empirical_normalization_until is None
+    env_cfg, train_cfg = task_registry.get_cfgs("go1_rough_asym_norm")
+    assert train_cfg.runner.empirical_normalization is True and env_cfg.env.num_privileged_obs == 253
+    assert task_registry.get_cfgs("go1_rough_asym")[1].runner.empirical_normalization is False
+    # a variant: go1_rough_asym's env class and env cfg under a second name, not a second env entry
+    from legged_gym_amd.envs.go1.go1 import Go1
+    assert task_registry.get_task_class("go1_rough_asym_norm") is Go1
+    assert env_cfg is task_registry.get_cfgs("go1_rough_asym")[0]
+    assert "go1_rough_asym_norm" not in task_registry.task_classes
+    with pytest.raises(ValueError):
+        task_registry.register_variant("x_norm", "no_such_task", train_cfg)
+
+
+@pytest.mark.parametrize("recurrent", [False, True])
+def test_runner_normalises_in_front_of_actor_and_critic(recurrent):
+    runner, env, cfg = make_runner(recurrent=recurrent)
+    nz = runner.obs_normalizer
+    assert nz is not None and runner.critic_obs_normalizer is nz and nz.width == env.num_obs
+    seen = []
+    orig_act = runner.alg.act
+
+    def act(obs, cobs):
+        seen.append((obs, cobs, nz.count))
+        return orig_act(obs, cobs)
+    runner.alg.act = act
+    runner.learn(1)
+    N, T = env.num_envs, cfg["runner"]["num_steps_per_env"]
+    assert nz.count == N * T + N, "once per step (one shared normaliser), plus the starting row"
+    assert [c for _, _, c in seen] == [N * (k + 1) for k in range(T)]
+    assert all(o is c for o, c, _ in seen), "one result for actor and critic"
+    assert all(torch.isfinite(o).all() for o, _, _ in seen)
+    stats = runner.last_iteration_stats
+    assert np.isfinite(stats["value_loss"]) and np.isfinite(stats["surrogate_loss"])
+    runner.learn(1)       # the starting row of a later learn() is already in the statistics
+    assert nz.count == 2 * N * T + N
+    obs = env.get_observations()
+    policy = runner.get_inference_policy()
+    with torch.inference_mode():
+        if recurrent:
+            runner.alg.actor_critic.reset()
+        got = policy(obs)
+        if recurrent:
+            runner.alg.actor_critic.reset()
+        want = runner.alg.actor_critic.act_inference(nz(obs, update=False))
+    assert torch.equal(got, want) and nz.count == 2 * N * T + N
+    raw = runner.alg.actor_critic.act_inference(obs) if not recurrent else None
+    assert raw is None or not torch.equal(raw, got)
+
+
+def test_runner_until_freezes_the_statistics():
+    runner, env, cfg = make_runner(until=24)
+    runner.learn(1)
+    assert runner.obs_normalizer.count == 24      # 8 envs: the starting row and two steps
+
+
+def test_runner_checkpoint_round_trip_and_mismatches(tmp_path):
+    runner, env, cfg = make_runner(tmp_path)
+    runner.learn(1)
+    path = os.path.join(tmp_path, "model_1.pt")
+    d = torch.load(path, weights_only=True)
+    assert set(d) == {"model_state_dict", "optimizer_state_dict", "iter", "infos", "obs_norm_state_dict"}
+    other, _, _ = make_runner()
+    other.load(path)
+    assert other.obs_normalizer.count == runner.obs_normalizer.count > 0
+    a, b = runner.obs_normalizer.state_dict(), other.obs_normalizer.state_dict()
+    assert all(torch.equal(a[k], b[k]) for k in a)
+    (tmp_path / "plain").mkdir()
+    plain, _, _ = make_runner(tmp_path / "plain", norm=False)
+    assert plain.obs_normalizer is None and plain.critic_obs_normalizer is None
+    with pytest.raises(ValueError, match="empirical_normalization"):
+        plain.load(path)
+    plain.learn(1)
+    plain_path = os.path.join(tmp_path / "plain", "model_1.pt")
+    assert set(torch.load(plain_path, weights_only=True)) == {"model_state_dict", "optimizer_state_dict", "iter",
+                                                             "infos"}
+    with pytest.raises(ValueError, match="empirical_normalization"):
+        other.load(plain_path)
+    assert plain.get_inference_policy() == plain.alg.actor_critic.act_inference
+
+
+# ---------------------------------------------------------------------- export
+def trained_normalizer(width):
+    nz = EmpiricalNormalization(width)
+    run_calls(nz, ref.make_batches(R + 1, width))
+    return nz
+
+
+def y_tolerance(nz, x, y):
+    inv, mean = nz.inv().double(), nz.state_dict()["mean"]
+    return 2.0 ** -22 * ((x.double().abs() + mean.abs()) * inv + y.double().abs())
+
+
+def test_exported_mlp_policy_takes_raw_observations(tmp_path):
+    from legged_gym_amd.rl.actor_critic import ActorCritic
+    from legged_gym_amd.utils import export_policy_as_jit
+    torch.manual_seed(0)
+    ac = ActorCritic(48, 48, 12, [16, 8], [16, 8])
+    nz = trained_normalizer(48)
+    x = torch.from_numpy(ref.make_batches(5, 48, calls=1, seed=7)[0])
+    export_policy_as_jit(ac, str(tmp_path / "norm"), normalizer=nz)
+    pol = torch.jit.load(str(tmp_path / "norm" / "policy_1.pt"))
+    front = getattr(pol, "0")
+    y = nz(x, update=False)
+    assert ((front(x) - y).abs().double() <= y_tolerance(nz, x, y)).all()
+    assert front.mean.dtype == front.inv.dtype == torch.float32
+    assert torch.equal(pol(x), ac.actor(front(x)))
+    torch.testing.assert_close(pol(x), ac.actor(y), atol=1e-5, rtol=1e-5)
+    # without the argument: today's export
+    export_policy_as_jit(ac, str(tmp_path / "plain"))
+    plain = torch.jit.load(str(tmp_path / "plain" / "policy_1.pt"))
+    assert torch.equal(plain(x), ac.actor(x)) and not torch.equal(plain(x), pol(x))
+    assert sorted(plain.state_dict()) == sorted(ac.actor.state_dict())
+
+
+def test_exported_lstm_policy_takes_raw_observations(tmp_path):
+    from legged_gym_amd.rl.actor_critic import ActorCriticRecurrent
+    from legged_gym_amd.utils.helpers import PolicyExporterLSTM, export_policy_as_jit
+    torch.manual_seed(0)
+    ac = ActorCriticRecurrent(48, 48, 12, [16, 8], [16, 8], rnn_type="lstm", rnn_hidden_size=16, rnn_num_layers=1)
+    nz = trained_normalizer(48)
+    x = torch.from_numpy(ref.make_batches(3, 48, calls=1, seed=7)[0]).unsqueeze(1)
+    export_policy_as_jit(ac, str(tmp_path / "norm"), normalizer=nz)
+    export_policy_as_jit(ac, str(tmp_path / "plain"))
+    pol = torch.jit.load(str(tmp_path / "norm" / "policy_lstm_1.pt"))
+    plain = torch.jit.load(str(tmp_path / "plain" / "policy_lstm_1.pt"))
+    y = torch.stack([nz(x[i], update=False) for i in range(3)])
+    assert ((pol.normalizer(x[0]) - y[0]).abs().double() <= y_tolerance(nz, x[0], y[0])).all()
+    with torch.no_grad():
+        want = ac.actor(ac.memory_a.rnn(y)[0][:, 0])
+        want_plain = ac.actor(ac.memory_a.rnn(x)[0][:, 0])
+    torch.testing.assert_close(torch.stack([pol(x[i]) for i in range(3)])[:, 0], want, atol=1e-5, rtol=1e-5)
+    torch.testing.assert_close(torch.stack([plain(x[i]) for i in range(3)])[:, 0], want_plain, atol=1e-5, rtol=1e-5)
+    eager = PolicyExporterLSTM(ac)      # the call without the argument still works
+    assert torch.equal(eager(x[0]), PolicyExporterLSTM(ac, None)(x[0]))
+
+
+# ---------------------------------------------------------------------- data parallel (gloo)
+def _free_port():
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    port = s.getsockname()[1]
+    s.close()
+    return port
+
+
+def _dp_worker(rank, world, port, out_q):
+    import torch.distributed as dist
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    nz = EmpiricalNormalization(253)
+    half = 2 * R
+    ys = [nz(torch.from_numpy(b[rank * half:(rank + 1) * half])) for b in ref.make_batches(2 * half, 253)]
+    d = nz.state_dict()
+    out_q.put((rank, nz.count, d["count"].numpy(), d["mean"].numpy(), d["m2"].numpy(), [y.numpy() for y in ys]))
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+def test_two_ranks_equal_one_process_bitwise():
+    """2 ranks x 2R rows == 1 process x 4R rows: every rank folds all ranks' partials in rank order."""
+    batches = ref.make_batches(4 * R, 253)
+    one = EmpiricalNormalization(253)
+    ys = run_calls(one, batches)
+    d = one.state_dict()
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_dp_worker, args=(r, 2, port, q)) for r in range(2)]
+    for p in procs:
+        p.start()
+    got = sorted([q.get(timeout=120) for _ in range(2)], key=lambda t: t[0])
+    for p in procs:
+        p.join(timeout=120)
+        assert p.exitcode == 0
+    for rank, count, n, mean, m2, yr in got:
+        assert count == one.count == 3 * 4 * R and int(n) == count
+        assert np.array_equal(mean, d["mean"].numpy()) and np.array_equal(m2, d["m2"].numpy()), rank
+        for k in range(3):
+            assert np.array_equal(yr[k], ys[k][rank * 2 * R:(rank + 1) * 2 * R].numpy()), (rank, k)
