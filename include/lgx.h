@@ -403,6 +403,53 @@ typedef struct lgx_actuator_rand_desc {
 } lgx_actuator_rand_desc;
 int lgx_bind_actuator_rand(lgx_sim* sim, const lgx_actuator_rand_desc* desc);
 
+/* Command curriculum (cfg.commands.curriculum; legged_robot.py:165-167, 189-190, 465-474): while
+ * bound, every entry point that takes common_step_counter (lgx_step, lgx_step_from,
+ * lgx_post_physics, lgx_post_physics_fused, lgx_reset_idx) decides on the host, from the counter and
+ * max_episode_length alone (lgx_is_curriculum_step: no sync, no readback), whether this is a
+ * curriculum step.  On those steps only it enqueues, after its post-physics / reset launch and on
+ * the same stream, two small launches; every other step issues exactly the launches of a sim that
+ * never bound.
+ *   decide: over the envs that launch reset (lgx_reset_idx: the listed ids), none: nothing changes;
+ *           lhs = mean(episode_sums[tracking_lin_vel], this step's reward included) /
+ *           max_episode_length, float32, from the launch's own block partials in the fixed order of
+ *           the episode extras.  If lhs > threshold:
+ *             lo = min(max(lo - 0.5, -max_curriculum), 0), hi = min(max(hi + 0.5, 0), max_curriculum)
+ *           of cmd_ranges[0] (lin_vel_x; np.clip's order) in the sim's device params.
+ *   patch:  if the range moved, the envs reset in that step draw their x / y command again from the
+ *           same draws (LGX_DRAW_RESET_CMD, this step; injected draws honoured) with the new range
+ *           and the 0.2 m/s gate: commands[e, 0:2] and, on the step / post-physics routes, their
+ *           published copies - obs columns 9, 10, the obs part of a bound history row, the clean
+ *           part of a bound privileged row (scale, then clip to clip_obs) - are what the launch
+ *           would have written had it sampled from the new range.  Envs that only hit their
+ *           resampling interval keep the command they drew from the old range, as in the reference.
+ * state (caller-owned device float[4], written at bind and by every decide launch that saw a reset):
+ *   [0] lo, [1] hi, [2] number of times the range moved since bind, [3] the last lhs.
+ * threshold: float32(0.8 * reward_scales["tracking_lin_vel"]) of the reference's float64 product.
+ * The device owns the range from lgx_sim_create on: nothing uploads lgx_env_params again, and
+ * lgx_set_command_range is the host's way to set it.  One sim decides from its own envs.
+ * desc == NULL unbinds.  LGX_EINVAL (message in lgx_last_error) for a null sim or state, a
+ * max_curriculum that is negative or not finite, a threshold that is not finite, a sim without a
+ * tracking_lin_vel reward term of positive scale (the reference raises KeyError), or non-zero
+ * command columns (9..11) of noise_scale_vec (the reference zeroes them; a zero noise term is what
+ * keeps the rewritten observation entries the launch's own). */
+typedef struct lgx_cmd_curriculum_desc {
+  float max_curriculum;
+  float threshold;
+  float* state;
+} lgx_cmd_curriculum_desc;
+int lgx_bind_command_curriculum(lgx_sim* sim, const lgx_cmd_curriculum_desc* desc);
+/* sizeof(lgx_cmd_curriculum_desc) and the offsets of max_curriculum, threshold, state */
+void lgx_cmd_curriculum_desc_layout(int64_t out[4]);
+/* The host's test for a curriculum step: common_step_counter % max_episode_length == 0 with the
+ * integer-valued float length of lgx_env_params (counter 0 included); 0 for a length <= 0. */
+int32_t lgx_is_curriculum_step(int64_t common_step_counter, float max_episode_length);
+/* Stream-ordered write of cmd_ranges[k] = {lo, hi} (k: 0 lin_vel_x, 1 lin_vel_y, 2 ang_vel_yaw,
+ * 3 heading) in the sim's device params, and of state[0], state[1] when k == 0 and a curriculum is
+ * bound; launches behind it on `stream` sample from the new range.  LGX_EINVAL for a null sim, k
+ * outside [0, 3], or bounds that are not finite or have lo > hi. */
+int lgx_set_command_range(lgx_sim* sim, int32_t k, float lo, float hi, void* stream);
+
 /* Data-parallel gradient all-reduce over RCCL (SURVEY §8(b) lgx_allreduce_grads; §8(e): the
  * gradient average of a multi-GPU PPO update, one rank per GPU).  One communicator per rank,
  * created collectively from a unique id that rank 0 draws and the caller distributes (e.g. over

@@ -1,6 +1,8 @@
 // C-ABI implementation (include/lgx.h): validation, device-resident model/params, launch
 // sequencing.  No host synchronisation in any step-path call; errors are reported through
 // return codes + a thread-local message, never by exceptions across the ABI.
+#include <math.h>
+#include <stddef.h>
 #include <stdio.h>
 #include <string.h>
 
@@ -46,6 +48,7 @@ struct lgx_sim {
   lgx_priv_args priv;      // lgx_bind_privileged_obs (buf NULL: no privileged row)
   lgx_hist_args hist;      // lgx_bind_obs_history (row NULL: no history; age is owned here)
   lgx_act_rand_args arand; // lgx_bind_actuator_rand (prev NULL: no tables; prev is owned here)
+  lgx_cmdcur_args ccur;    // lgx_bind_command_curriculum (state NULL: none; changed is owned here)
   // Go1 actuator net off the critical path: its output (dVel) is not read by the step
   // (go1.py:71-73), so it runs on an auxiliary stream concurrently with post-physics and the
   // next policy forward; the next physics launch (which rewrites model_ins) waits for it.
@@ -208,6 +211,7 @@ int lgx_sim_create(const lgx_model* model, const lgx_env_params* params, const l
   s->priv = lgx_priv_args{};
   s->hist = lgx_hist_args{};
   s->arand = lgx_act_rand_args{};
+  s->ccur = lgx_cmdcur_args{};
   s->aux = nullptr;
   s->aux_in = s->aux_done = nullptr;
   s->aux_pending = false;
@@ -242,6 +246,7 @@ int lgx_sim_destroy(lgx_sim* s) {
   for (hipEvent_t e : s->pool) (void)hipEventDestroy(e);
   (void)hipFree(s->hist.age);
   (void)hipFree(s->arand.prev);
+  (void)hipFree(s->ccur.changed);
   (void)hipFree(s->d_model);
   (void)hipFree(s->d_params);
   delete s;
@@ -425,6 +430,94 @@ int lgx_bind_actuator_rand(lgx_sim* s, const lgx_actuator_rand_desc* d) {
   return hip_check(hipDeviceSynchronize(), "lgx_bind_actuator_rand: hipDeviceSynchronize");
 }
 
+void lgx_cmd_curriculum_desc_layout(int64_t out[4]) {
+  out[0] = (int64_t)sizeof(lgx_cmd_curriculum_desc);
+  out[1] = (int64_t)offsetof(lgx_cmd_curriculum_desc, max_curriculum);
+  out[2] = (int64_t)offsetof(lgx_cmd_curriculum_desc, threshold);
+  out[3] = (int64_t)offsetof(lgx_cmd_curriculum_desc, state);
+}
+
+// common_step_counter % max_episode_length == 0 with an integer-valued float length (legged_robot.py:165)
+int32_t lgx_is_curriculum_step(int64_t common_step_counter, float max_episode_length) {
+  if (!(max_episode_length > 0.f)) return 0;
+  return fmod((double)common_step_counter, (double)max_episode_length) == 0.0 ? 1 : 0;
+}
+
+int lgx_bind_command_curriculum(lgx_sim* s, const lgx_cmd_curriculum_desc* d) {
+  if (!s) return fail(LGX_EINVAL, "lgx_bind_command_curriculum: null sim");
+  if (!d) {
+    int rc = s->ccur.changed ? hip_check(hipFree(s->ccur.changed), "lgx_bind_command_curriculum: hipFree(changed)") : 0;
+    s->ccur = lgx_cmdcur_args{};
+    return rc;
+  }
+  if (!d->state) return fail(LGX_EINVAL, "lgx_bind_command_curriculum: null state");
+  if (!(d->max_curriculum >= 0.f) || !isfinite(d->max_curriculum) || !isfinite(d->threshold))
+    return fail(LGX_EINVAL, "lgx_bind_command_curriculum: max_curriculum must be finite and >= 0, threshold finite");
+  const lgx_env_params& p = s->params;
+  if (!(p.max_episode_length > 0.f)) return fail(LGX_EINVAL, "lgx_bind_command_curriculum: max_episode_length must be > 0");
+  int row = -1;
+  for (int t = 0; t < p.num_terms; ++t)
+    if (p.term_ids[t] == LGX_R_TRACKING_LIN_VEL) row = t;
+  if (row < 0 || !(p.term_scales[row] > 0.f))
+    return fail(LGX_EINVAL, "lgx_bind_command_curriculum: the curriculum reads the tracking_lin_vel episode sum: that "
+                            "reward term must be present with a positive scale");
+  for (int i = 9; i < 12; ++i)
+    if (p.noise_scale_vec[i] != 0.f)
+      return fail(LGX_EINVAL, "lgx_bind_command_curriculum: the command columns (9..11) of noise_scale_vec must be zero");
+  // a setup call, ordered against launches on any stream by draining the device (as lgx_bind_actuator_rand)
+  int32_t* changed = s->ccur.changed;
+  if (!changed) {
+    if (int rc = hip_check(hipMalloc(&changed, sizeof(int32_t)), "lgx_bind_command_curriculum: hipMalloc(changed)")) return rc;
+  }
+  s->ccur = lgx_cmdcur_args{d->state, changed, d->max_curriculum, d->threshold, row};
+  if (int rc = hip_check(hipDeviceSynchronize(), "lgx_bind_command_curriculum: hipDeviceSynchronize")) return rc;
+  if (int rc = hip_check(hipMemset(changed, 0, sizeof(int32_t)), "lgx_bind_command_curriculum: hipMemset(changed)")) return rc;
+  if (int rc = launch_check(lgx_launch_cmd_curriculum_init(s->d_params, d->state, nullptr),
+                            "lgx_bind_command_curriculum: launch"))
+    return rc;
+  return hip_check(hipDeviceSynchronize(), "lgx_bind_command_curriculum: hipDeviceSynchronize");
+}
+
+int lgx_set_command_range(lgx_sim* s, int32_t k, float lo, float hi, void* stream) {
+  if (!s) return fail(LGX_EINVAL, "lgx_set_command_range: null sim");
+  if (k < 0 || k > 3) return fail(LGX_EINVAL, "lgx_set_command_range: k must be 0 (lin_vel_x) .. 3 (heading)");
+  if (!isfinite(lo) || !isfinite(hi) || lo > hi) return fail(LGX_EINVAL, "lgx_set_command_range: need finite lo <= hi");
+  s->params.cmd_ranges[k][0] = lo;   // the host copy is never uploaded again: the device owns the range
+  s->params.cmd_ranges[k][1] = hi;
+  return launch_check(lgx_launch_set_command_range(s->d_params, k, lo, hi, k == 0 ? s->ccur.state : nullptr,
+                                                   (hipStream_t)stream),
+                      "lgx_set_command_range: launch");
+}
+
+// The curriculum work of an entry point that takes common_step_counter, after its post-physics
+// (ids == nullptr: the launch's reset flags, obs patched) or reset (the n listed ids, commands
+// only) launch on `st`.  Decided here from the counter alone: every other step enqueues nothing.
+static int command_curriculum(lgx_sim* s, int64_t step, hipStream_t st, const int32_t* ids, int32_t n) {
+  if (!s->ccur.state || !lgx_is_curriculum_step(step, s->params.max_episode_length)) return 0;
+  lgx_cmdcur_patch_args pa{};
+  pa.changed = s->ccur.changed;
+  pa.step = step;
+  pa.draws = s->draws;
+  pa.commands = s->bufs.commands;
+  if (ids) {
+    pa.ids = ids;
+    pa.n = n;
+    pa.tag = 1u;
+  } else {
+    pa.reset = s->bufs.reset;
+    pa.n = s->params.num_envs;
+    pa.tag = 0u;
+    pa.obs = s->bufs.obs;
+    pa.hist = s->hist.row;
+    pa.hist_width = s->hist.width;
+    pa.priv = s->priv.buf;
+    pa.priv_width = s->priv.width;
+  }
+  const int32_t nblocks = (pa.n + LGX_ENV_BLOCK - 1) / LGX_ENV_BLOCK;
+  return launch_check(lgx_launch_cmd_curriculum(s->d_params, s->bufs.scratch, nblocks, s->n_term_rows, s->ccur, pa, st),
+                      "command curriculum: launch");
+}
+
 int lgx_rebind_extras(lgx_sim* s, float* snapshot) {
   if (!s) return fail(LGX_EINVAL, "lgx_rebind_extras: null sim");
   s->extras_snapshot = snapshot;
@@ -475,10 +568,12 @@ int lgx_ground_contact(lgx_sim* s, const float* points, int32_t n, float* out, v
 
 int lgx_post_physics(lgx_sim* s, int64_t step, void* stream) {
   if (!s) return fail(LGX_EINVAL, "lgx_post_physics: null sim");
-  return launch_check(lgx_launch_post_physics(s->d_params, s->bufs, s->params.num_envs, s->params.num_obs, s->n_term_rows,
-                                              s->params.measure_heights, step, s->draws, s->extras_snapshot, s->priv,
-                                              s->hist, (hipStream_t)stream),
-                      "lgx_post_physics: launch");
+  if (int rc = launch_check(lgx_launch_post_physics(s->d_params, s->bufs, s->params.num_envs, s->params.num_obs,
+                                                    s->n_term_rows, s->params.measure_heights, step, s->draws,
+                                                    s->extras_snapshot, s->priv, s->hist, (hipStream_t)stream),
+                            "lgx_post_physics: launch"))
+    return rc;
+  return command_curriculum(s, step, (hipStream_t)stream, nullptr, 0);
 }
 
 static int post_physics_fused(lgx_sim* s, int64_t step, hipStream_t st, bool sample);
@@ -517,7 +612,7 @@ static int post_physics_fused(lgx_sim* s, int64_t step, hipStream_t st, bool sam
                                                   s->bufs.act_net_scale, s->priv, s->hist, st),
                       "lgx_step: post-physics + actuator launch");
     lgx_timing = lgx_timing_slot{};
-    return rc;
+    return rc ? rc : command_curriculum(s, step, st, nullptr, 0);
   }
   if (act_net) {
     // UniNet on every (substep, env, leg) row of this step's model_ins; result = dVel
@@ -589,9 +684,12 @@ int lgx_profile_collect(lgx_sim* s, double* ms, int64_t* count) {
 int lgx_reset_idx(lgx_sim* s, const int32_t* env_ids, int32_t n, int64_t step, int32_t init_done, void* stream) {
   if (!s || n < 0 || (n > 0 && !env_ids)) return fail(LGX_EINVAL, "lgx_reset_idx: bad arguments");
   if (n > s->params.num_envs) return fail(LGX_EINVAL, "lgx_reset_idx: more ids than envs");
-  return launch_check(lgx_launch_reset_idx(s->d_params, s->bufs, s->params.num_envs, s->n_term_rows, env_ids, n, step,
-                                           init_done, s->draws, s->extras_snapshot, s->hist.age, (hipStream_t)stream),
-                      "lgx_reset_idx: launch");
+  if (int rc = launch_check(lgx_launch_reset_idx(s->d_params, s->bufs, s->params.num_envs, s->n_term_rows, env_ids, n,
+                                                 step, init_done, s->draws, s->extras_snapshot, s->hist.age,
+                                                 (hipStream_t)stream),
+                            "lgx_reset_idx: launch"))
+    return rc;
+  return n > 0 ? command_curriculum(s, step, (hipStream_t)stream, env_ids, n) : 0;
 }
 
 int lgx_actuator_mlp(const float* in, float* out, int64_t rows, const float* w, const float* out_scale, void* stream) {

@@ -95,6 +95,39 @@ int lgx_launch_post_physics_act_hist(const lgx_env_params* dp, const lgx_buffers
 int lgx_launch_reset_idx(const lgx_env_params* dp, const lgx_buffers& b, int32_t n_envs, int32_t n_term_rows,
                          const int32_t* ids, int32_t n, int64_t step, int32_t init_done, const float* draws,
                          float* extras_snapshot, int32_t* hist_age, hipStream_t stream);
+// the command curriculum of a sim (lgx_bind_command_curriculum, checked there), passed by value to
+// the decide launch; state == nullptr: nothing bound.  changed: the sim's device int32, written by
+// every decide launch (1: the range moved) and read by the patch launch behind it
+struct lgx_cmdcur_args {
+  float* state;          // the caller's float[4]: lo, hi, number of widenings, last left-hand side
+  int32_t* changed;
+  float max_curriculum, threshold;
+  int32_t row;           // tracking_lin_vel's row of the block partials (= of episode_sums)
+};
+// what the patch launch rewrites for the envs that reset in this step: n = num_envs and the reset
+// flags (post-physics routes), or the n listed ids (lgx_reset_idx; reset unused); obs == nullptr:
+// commands only, else obs and, where bound, the history row (hist) and the privileged row (priv)
+struct lgx_cmdcur_patch_args {
+  const int32_t* changed;
+  const uint8_t* reset;
+  const int32_t* ids;
+  int32_t n;
+  uint32_t tag;          // the Philox tag of the reset's draws: 0 post-physics, 1 lgx_reset_idx
+  int64_t step;
+  const float* draws;    // injected draws or nullptr
+  float* commands;
+  float* obs;
+  float* hist;
+  float* priv;
+  int32_t hist_width, priv_width;
+};
+// lgx_cmd_curriculum.hip: decide (one wave over the nblocks partial rows of the launch before it;
+// count_row = the reset-count row) + patch; nothing is launched for nblocks <= 0 or pa.n <= 0
+int lgx_launch_cmd_curriculum(lgx_env_params* dp, const float* scratch, int32_t nblocks, int32_t count_row,
+                              const lgx_cmdcur_args& cc, const lgx_cmdcur_patch_args& pa, hipStream_t stream);
+int lgx_launch_cmd_curriculum_init(const lgx_env_params* dp, float* state, hipStream_t stream);
+// cmd_ranges[k] = {lo, hi} in the device params, and state[0:2] when state != nullptr
+int lgx_launch_set_command_range(lgx_env_params* dp, int32_t k, float lo, float hi, float* state, hipStream_t stream);
 // wg_per_cu: persistent workgroups per CU of the weight-stationary kernel (2 when it owns the
 // chip, 1 when it shares the CUs with concurrent work on another stream)
 int lgx_launch_actuator_mlp(const float* in, float* out, int64_t rows, const float* w, const float* out_scale,

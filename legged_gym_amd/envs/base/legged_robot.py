@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from legged_gym_amd import LEGGED_GYM_ROOT_DIR
-from legged_gym_amd.envs.base import actuator_rand, history, privileged
+from legged_gym_amd.envs.base import actuator_rand, command_curriculum, history, privileged
 from legged_gym_amd.envs.base.base_task import BaseTask
 from legged_gym_amd.sim import abi
 from legged_gym_amd.sim.model import RobotAsset, build_model, resolve_asset_path
@@ -118,6 +118,20 @@ class LgxBackend:
         d = abi.LgxActuatorRandDesc(p(kp_scale), p(kd_scale), p(lag))
         self._check(self.lib.lgx_bind_actuator_rand(self.handle, C.byref(d)), "lgx_bind_actuator_rand")
 
+    def bind_command_curriculum(self, state, max_curriculum, threshold):
+        """lgx_bind_command_curriculum: the device float32[4] state {lo, hi, widenings, last lhs} the
+        decide launch writes, and the two numbers of the rule; state None unbinds.  The caller keeps
+        the tensor alive."""
+        if state is None:
+            self._check(self.lib.lgx_bind_command_curriculum(self.handle, None), "lgx_bind_command_curriculum")
+            return
+        d = abi.LgxCmdCurriculumDesc(max_curriculum, threshold, state.data_ptr())
+        self._check(self.lib.lgx_bind_command_curriculum(self.handle, C.byref(d)), "lgx_bind_command_curriculum")
+
+    def set_command_range(self, k, lo, hi):
+        """lgx_set_command_range: row k of the device-resident command ranges, stream-ordered."""
+        self._check(self.lib.lgx_set_command_range(self.handle, k, lo, hi, self.stream()), "lgx_set_command_range")
+
     def sync_aux(self):
         self._check(self.lib.lgx_sync_aux(self.handle, self.stream()), "lgx_sync_aux")
 
@@ -182,6 +196,7 @@ class LeggedRobot(BaseTask):
         else:
             self.actions.copy_(actions)        # clipped in place by the kernel (:85-86)
             self._backend.step(self.common_step_counter)
+        self._after_curriculum_step()
         self._publish_extras(snap)
         return self.obs_buf, self.privileged_obs_buf, self.rew_buf, self.reset_buf, self.extras
 
@@ -196,6 +211,7 @@ class LeggedRobot(BaseTask):
             self._backend.post_physics(self.common_step_counter, fused=True)
         else:
             self._backend.post_physics(self.common_step_counter)
+        self._after_curriculum_step()
         self._publish_extras(snap)
 
     def simulate(self, n=1):
@@ -209,6 +225,7 @@ class LeggedRobot(BaseTask):
         ids = torch.as_tensor(env_ids, device=self.device).to(torch.int32).contiguous()
         snap = self._next_extras_snapshot()
         self._backend.reset_idx(ids, self.common_step_counter, self.init_done)
+        self._after_curriculum_step()
         self._publish_extras(snap)
 
     def _next_obs_buffer(self):
@@ -256,6 +273,8 @@ class LeggedRobot(BaseTask):
         ep = {}
         for key, row in self._extras_rows:
             ep[key] = snap[row]
+        if self.command_curriculum_state is not None:   # the current upper bound (legged_robot.py:189-190)
+            ep["max_command_x"] = self._max_command_x
         self.extras["episode"] = ep
         if self.cfg.env.send_timeouts:
             self.extras["time_outs"] = self._extras_time_outs
@@ -615,10 +634,12 @@ class LeggedRobot(BaseTask):
         layout = self._privileged_layout()
         hist_layout = self._history_layout()
         tables = self._actuator_rand_tables()
+        curriculum = self._command_curriculum_rule()
         self._backend = self._make_backend(self._lgx_model, p, b)
         self._bind_privileged_obs(layout)
         self._bind_obs_history(hist_layout)
         self._bind_actuator_rand(tables)
+        self._bind_command_curriculum(curriculum)
 
     def _privileged_layout(self):
         """The critic's row `[clean obs | cfg.privileged.terms]` (envs/base/privileged.py), or None
@@ -665,6 +686,54 @@ class LeggedRobot(BaseTask):
                              "actuator tables (the CPU oracle backend of the tests has none; the lgx backend "
                              "reads them in its physics launch)")
         self._backend.bind_actuator_rand(self.kp_scale, self.kd_scale, self.action_lag)
+
+    def _command_curriculum_rule(self):
+        """(max_curriculum, threshold) of cfg.commands.curriculum (envs/base/command_curriculum.py), or
+        None with the switch off; ValueError for a config the rule cannot run on."""
+        if not getattr(self.cfg.commands, "curriculum", False):
+            return None
+        return command_curriculum.validate(self.cfg.commands, self.reward_scales, self.noise_scale_vec.cpu().numpy())
+
+    def _bind_command_curriculum(self, rule):
+        """Allocate the curriculum's device state {lo, hi, widenings, last lhs}, publish it as
+        env.command_curriculum_state and bind it (lgx_bind_command_curriculum).  From here on the
+        device owns the lin_vel_x range: env.command_ranges is the host's copy (sync_command_ranges)."""
+        self.command_curriculum_state = self._max_command_x = None
+        if rule is None:
+            return
+        if not hasattr(self._backend, "bind_command_curriculum"):
+            raise ValueError(f"commands.curriculum: the backend {type(self._backend).__name__} cannot bind a command "
+                             "curriculum (the CPU oracle backend of the tests has none; the lgx backend decides "
+                             "and resamples on the device)")
+        self.command_curriculum_state = torch.zeros(4, dtype=torch.float, device=self.device)
+        self._backend.bind_command_curriculum(self.command_curriculum_state, float(rule[0]), float(rule[1]))
+        self._max_command_x = self.command_curriculum_state[1].clone()
+
+    def _after_curriculum_step(self):
+        """extras["episode"]["max_command_x"]: a fresh 0-d device tensor after each curriculum step (the
+        host knows which steps those are: no sync), the same tensor in between."""
+        if self.command_curriculum_state is not None and command_curriculum.is_curriculum_step(
+                self.common_step_counter, self.max_episode_length):
+            self._max_command_x = self.command_curriculum_state[1].clone()
+
+    def set_command_range(self, name, lo, hi):
+        """Set cfg.commands.ranges.<name> at run time (play.py-style users): the device-resident range
+        (lgx_set_command_range, stream-ordered: later launches sample from it) and env.command_ranges."""
+        k = command_curriculum.RANGE_NAMES.index(name)
+        lo, hi = float(lo), float(hi)
+        self.command_ranges[name] = [lo, hi]
+        self._lgx_params.cmd_ranges[k][0], self._lgx_params.cmd_ranges[k][1] = lo, hi
+        if hasattr(self._backend, "set_command_range"):
+            self._backend.set_command_range(k, lo, hi)
+            if k == 0 and self.command_curriculum_state is not None:
+                self._max_command_x = self.command_curriculum_state[1].clone()
+
+    def sync_command_ranges(self):
+        """Refresh env.command_ranges["lin_vel_x"] from the device (a host sync; never on the step path)."""
+        if self.command_curriculum_state is not None:
+            lo, hi = self.command_curriculum_state[:2].tolist()
+            self.command_ranges["lin_vel_x"] = [lo, hi]
+        return self.command_ranges
 
     def _history_layout(self):
         """The actor's row `[obs | cfg.history.frames frames]` (envs/base/history.py), or None

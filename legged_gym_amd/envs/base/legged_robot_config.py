@@ -43,8 +43,8 @@ class LeggedRobotCfg(BaseConfig):
         slope_treshold = 0.75       # (sic) trimesh only
 
     class commands:  # ref :72-82
-        curriculum = False
-        max_curriculum = 1.
+        curriculum = False          # widen lin_vel_x by 0.5 m/s per bound as tracking improves (ref :465-474;
+        max_curriculum = 1.         # decided and resampled on the device), up to +-max_curriculum
         num_commands = 4            # vx, vy, yaw rate, heading
         resampling_time = 10.
         heading_command = True

@@ -9,6 +9,8 @@ row (noise-free observations + the randomised friction / base mass + 
 go1_rough_hist; `Go1RoughAsymHistCfg` pairs the history with the privileged critic (not registered).
 `Go1RoughActRandCfg` is go1_rough with per-env drive gains and action latency,
 registered as go1_rough_actrand.
+`Go1RoughCmdCurCfg` is go1_rough with the command curriculum, registered as
+go1_rough_cmdcur.
 """
 from legged_gym_amd.envs.base.legged_robot_config import LeggedRobotCfg, LeggedRobotCfgPPO
 
@@ -130,6 +132,18 @@ class Go1RoughActRandCfg(Go1RoughTerrainCfg):
         randomize_kp = True
         randomize_kd = True
         randomize_lag = True
+
+
+class Go1RoughCmdCurCfg(Go1RoughTerrainCfg):
+    """go1_rough with the reference's command curriculum (commands.curriculum, legged_robot.py:465-474):
+    lin_vel_x starts half as wide as go1_rough's and widens by 0.5 m/s per bound, up to go1_rough's
+    range, whenever the envs that reset on a curriculum step tracked their velocity command well."""
+    class commands(Go1RoughTerrainCfg.commands):
+        curriculum = True
+        max_curriculum = Go1RoughTerrainCfg.commands.ranges.lin_vel_x[1]
+
+        class ranges(Go1RoughTerrainCfg.commands.ranges):
+            lin_vel_x = [0.5 * v for v in Go1RoughTerrainCfg.commands.ranges.lin_vel_x]
 
 
 class Go1RoughAsymHistCfg(Go1RoughAsymCfg):

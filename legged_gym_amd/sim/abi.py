@@ -168,6 +168,10 @@ class LgxActuatorRandDesc(C.Structure):   # lgx_actuator_rand_desc (the draws: e
     _fields_ = [("kp_scale", C.c_void_p), ("kd_scale", C.c_void_p), ("lag", C.c_void_p)]
 
 
+class LgxCmdCurriculumDesc(C.Structure):   # lgx_cmd_curriculum_desc (the rule: envs/base/command_curriculum.py)
+    _fields_ = [("max_curriculum", f32), ("threshold", f32), ("state", C.c_void_p)]
+
+
 class LgxObsNormJob(C.Structure):   # lgx_obs_norm_job (rl/normalizer.py)
     _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("rows", i64), ("width", i32), ("update", i32),
                 ("parts", C.c_void_p), ("nparts", i64), ("state_in", C.c_void_p), ("state_out", C.c_void_p),
@@ -228,6 +232,10 @@ def declare(lib, prefix="lgx"):
             "bind_obs_history": (C.c_int, [vp, vp, vp, C.POINTER(LgxObsHistoryDesc)]),
             "rebind_obs_history": (C.c_int, [vp, vp, vp]),
             "bind_actuator_rand": (C.c_int, [vp, C.POINTER(LgxActuatorRandDesc)]),
+            "bind_command_curriculum": (C.c_int, [vp, C.POINTER(LgxCmdCurriculumDesc)]),
+            "cmd_curriculum_desc_layout": (None, [C.POINTER(C.c_int64)]),
+            "is_curriculum_step": (i32, [i64, C.c_float]),
+            "set_command_range": (C.c_int, [vp, i32, C.c_float, C.c_float, vp]),
             "sim_buffer": (C.c_int, [vp, i32, C.POINTER(vp), C.POINTER(i64), C.POINTER(i32), C.POINTER(i32)]),
             "ppo_gather_rows": (C.c_int, [vp, vp, vp, i64, i32, vp]),
             "ppo_act": (C.c_int, [C.POINTER(LgxPpoActArgs), vp]),
@@ -293,7 +301,7 @@ def declare(lib, prefix="lgx"):
 
 
 EXPORTED = ["lgx_last_error", "lgx_version", "lgx_physics_lane_split", "lgx_trimesh_build", "lgx_struct_sizes", "lgx_scratch_floats", "lgx_sim_create",
-            "lgx_sim_destroy", "lgx_step", "lgx_simulate", "lgx_post_physics", "lgx_post_physics_fused", "lgx_reset_idx", "lgx_set_draws", "lgx_rebind_obs", "lgx_rebind_extras", "lgx_bind_privileged_obs", "lgx_rebind_privileged_obs", "lgx_bind_obs_history", "lgx_rebind_obs_history", "lgx_bind_actuator_rand", "lgx_sim_buffer", "lgx_step_from", "lgx_drive_inputs", "lgx_ground_contact", "lgx_sync_aux",
+            "lgx_sim_destroy", "lgx_step", "lgx_simulate", "lgx_post_physics", "lgx_post_physics_fused", "lgx_reset_idx", "lgx_set_draws", "lgx_rebind_obs", "lgx_rebind_extras", "lgx_bind_privileged_obs", "lgx_rebind_privileged_obs", "lgx_bind_obs_history", "lgx_rebind_obs_history", "lgx_bind_actuator_rand", "lgx_bind_command_curriculum", "lgx_cmd_curriculum_desc_layout", "lgx_is_curriculum_step", "lgx_set_command_range", "lgx_sim_buffer", "lgx_step_from", "lgx_drive_inputs", "lgx_ground_contact", "lgx_sync_aux",
             "lgx_actuator_mlp", "lgx_actuator_lstm", "lgx_mlp_forward", "lgx_gae", "lgx_gae_norm_scratch", "lgx_gae_norm", "lgx_gae_parts", "lgx_adv_norm",
             "lgx_profile_enable", "lgx_profile_collect", "lgx_mlp_forward_batch",
             "lgx_ppo_gather_rows", "lgx_bias_act", "lgx_ppo_loss_partials_floats", "lgx_ppo_loss", "lgx_ppo_adapt_lr",

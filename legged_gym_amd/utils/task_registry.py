@@ -2,7 +2,7 @@
 
 Same API and behaviour as legged_gym/utils/task_registry.py:46-171 (register / get_task_class /
 get_cfgs / make_env / make_alg_runner, log-dir layout and resume), plus `register_variant`: a
-registered task under a second name with another train cfg.  The runner is the in-repo
+registered task under a second name with another train cfg and, optionally, another env cfg.  The runner is the in-repo
 rsl_rl-compatible `OnPolicyRunner` (legged_gym_amd.rl) unless `rsl_rl` is importable and
 `LGX_USE_RSL_RL=1` is set, in which case the upstream runner drops in unchanged.
 """
@@ -33,20 +33,24 @@ class TaskRegistry:
         self.env_cfgs = {}
         self.train_cfgs = {}
         self.variants = {}   # name -> the registered task it trains differently (register_variant)
+        self.variant_env_cfgs = {}   # name -> the variant's own env cfg, where it has one
 
     def register(self, name: str, task_class, env_cfg: "LeggedRobotCfg", train_cfg: "LeggedRobotCfgPPO"):
         self.task_classes[name] = task_class
         self.env_cfgs[name] = env_cfg
         self.train_cfgs[name] = train_cfg
 
-    def register_variant(self, name: str, base: str, train_cfg: "LeggedRobotCfgPPO"):
-        """`base` under a second name with a train cfg of its own: the same env class and the same
-        env cfg object, so `task_classes` / `env_cfgs` keep one entry per env (no reference
-        counterpart; `--task name` selects it like any task)."""
+    def register_variant(self, name: str, base: str, train_cfg: "LeggedRobotCfgPPO", env_cfg: "LeggedRobotCfg" = None):
+        """`base` under a second name with a train cfg of its own: the same env class and, unless
+        `env_cfg` gives the variant one of its own, the same env cfg object; `task_classes` /
+        `env_cfgs` keep one entry per registered env (no reference counterpart; `--task name` selects
+        it like any task)."""
         if base not in self.task_classes:
             raise ValueError(f"Task with name: {base} was not registered")
         self.variants[name] = base
         self.train_cfgs[name] = train_cfg
+        if env_cfg is not None:
+            self.variant_env_cfgs[name] = env_cfg
 
     def _env_name(self, name):
         return self.variants.get(name, name)
@@ -56,7 +60,7 @@ class TaskRegistry:
 
     def get_cfgs(self, name) -> Tuple["LeggedRobotCfg", "LeggedRobotCfgPPO"]:
         train_cfg = self.train_cfgs[name]
-        env_cfg = self.env_cfgs[self._env_name(name)]
+        env_cfg = self.variant_env_cfgs.get(name) or self.env_cfgs[self._env_name(name)]
         env_cfg.seed = train_cfg.seed  # task_registry.py:63-64
         return env_cfg, train_cfg
 
