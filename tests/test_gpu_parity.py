@@ -19,6 +19,7 @@ import pytest
 import torch
 
 from oracle_backend import OracleBackend, make_env, load_oracle, uninet_torch_layout
+import reward_terms_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -246,10 +247,16 @@ def test_post_physics_matches_oracle_philox(envs_flat, seed):
     randomize_state(ora, gen)
     ora._contact_forces_full[:] = (torch.rand(ora._contact_forces_full.shape, generator=gen) - 0.3) * 4
     sync(ora, dev)
+    start = reward_terms_ref.capture_state(ora)
     ora.common_step_counter = dev.common_step_counter = 750  # push happens at 751
     ora.post_physics_step()
     dev.post_physics_step()
     torch.cuda.synchronize()
+    # each episode-sum row of the non-reset envs, and the rotated base vectors, within the derived
+    # float32 bound of the float64 reference on the same state (tests/reward_terms_ref.py) - kernel and oracle
+    for env in (dev, ora):
+        ratios = reward_terms_ref.compare_with_reference(env, start, sums_only=True)
+        assert ratios["envs"] >= 1, "test state should leave envs running"
     for name in ["obs_buf", "rew_buf", "commands", "feet_air_time", "root_states", "dof_state", "last_actions",
                  "last_dof_vel", "last_root_vel", "base_lin_vel", "base_ang_vel", "projected_gravity",
                  "_episode_sums_buf", "_extras_buf"]:
