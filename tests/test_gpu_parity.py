@@ -831,7 +831,11 @@ def _cassie_state(env, gen):
 @pytest.mark.parametrize("seed", [0, 1])
 def test_cassie_dense_physics_matches_float64(gpu, seed):
     """Cassie (2 legs x 6 joints: lgx_physics_dense_kernel) on its rough terrain: 4 substeps from
-    randomised states, HIP vs the float64 oracle with the derived tolerance (check_derived)."""
+    randomised states, HIP vs the float64 oracle with the derived tolerance (check_derived).
+    What these random states cover of the drive and limit branches, from the float64 records: a few
+    joints past a limit (seed 200: 5 decisions below, 1 above; seed 201: 5 above) and one saturated
+    drive decision each - asserted below.  Every joint of the 6-joint legs at both limits, at the
+    velocity clamp and saturated with both signs is test_gpu_physics_branches.py's Cassie case."""
     ora = make_env("cassie", num_envs=64, device="cpu", backend="oracle")
     dev = make_env("cassie", num_envs=64, device="cuda:0", backend="lgx")
     assert dev._lgx_model.leg_dof == 6
@@ -840,6 +844,10 @@ def test_cassie_dense_physics_matches_float64(gpu, seed):
     sync(ora, dev)
     dev.terrain_types.copy_(ora.terrain_types)
     t64 = float64_truth(ora, 4)
+    outside = sum(1 for r in t64.records if r[2] == 2 and r[4] != 0)
+    saturated = sum(1 for r in t64.records if r[2] == 1 and r[4] == 0)
+    implicit = sum(1 for r in t64.records if r[2] == 1 and r[4] == 1)
+    assert outside >= 4 and saturated >= 1 and implicit >= 3000, (outside, saturated, implicit)
     ora.simulate(4)
     dev.simulate(4)
     torch.cuda.synchronize()
