@@ -976,6 +976,46 @@ int lgx_ppo_gather_rows_padded(const float* src, float* dst, const int64_t* idx,
 int lgx_ppo_gather_rows_padded_dup(const float* src, float* dst, const int64_t* idx, int64_t rows, int32_t width,
                                    int32_t dst_ld, int64_t block, void* stream);
 
+/* Left-right symmetry augmentation of the rollout storage (rsl_rl 2.x symmetry_cfg.
+ * use_data_augmentation; lgx_symmetry.hip).  The storage arrays hold twice the rollout's rows; one
+ * launch writes, for r in [0, rows), row dst_row + r of every array from its row src_row + r:
+ *   observations, privileged_observations (when not NULL)   y[c] = sign[c] * x[perm[c]], own tables
+ *   actions, mu                                             through the action table
+ *   sigma                                                   through the action permutation, no sign
+ *   actions_log_prob, advantages, values, returns           copied
+ * so the update's kernels, which read everything through row indices, run unchanged over real rows
+ * and their mirror images (a PPO update: src_row 0, dst_row rows).  A table is a signed permutation
+ * (envs/base/symmetry.py); perm / sign are device pointers that the launch trusts:
+ * lgx_ppo_symmetry_check_table checks a table once, from host copies, when it is bound.
+ * LGX_EINVAL (message in lgx_last_error, nothing launched) for null args, rows < 1, negative or
+ * overlapping source / destination rows, num_obs or (with a privileged array) num_cobs outside
+ * [1, LGX_MAX_PRIV_OBS], num_actions outside [1, LGX_PPO_MAX_ACTIONS], or a null pointer the
+ * launch uses. */
+typedef struct lgx_symmetry_args {
+  int64_t rows;                      /* B = T * N transitions */
+  int64_t src_row, dst_row;          /* first source / destination row: |src_row - dst_row| >= rows */
+  int32_t num_obs, num_cobs, num_actions, pad;
+  float* observations;               /* [>= max(src, dst) + rows, num_obs] */
+  float* privileged_observations;    /* [.., num_cobs] or NULL */
+  float* actions;                    /* [.., num_actions] */
+  float* mu;
+  float* sigma;
+  float* actions_log_prob;           /* [..] */
+  float* advantages;
+  float* values;
+  float* returns;
+  const int32_t* obs_perm;           /* [num_obs] */
+  const float* obs_sign;
+  const int32_t* cobs_perm;          /* [num_cobs]; unused without privileged_observations */
+  const float* cobs_sign;
+  const int32_t* act_perm;           /* [num_actions] */
+  const float* act_sign;
+} lgx_symmetry_args;
+int lgx_ppo_symmetry_augment(const lgx_symmetry_args* args, void* stream);
+/* Host check of one table (host pointers): LGX_EINVAL for a null pointer, a width outside
+ * [1, LGX_MAX_PRIV_OBS], a perm entry outside [0, width) or a sign that is not +-1. */
+int lgx_ppo_symmetry_check_table(const int32_t* perm, const float* sign, int32_t width);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,7 +5,8 @@ with a privileged critic: env.num_privileged_obs + cfg.privileged), go1_rough_as
 with runner.empirical_normalization: running mean / std in front of actor and critic), go1_rough_hist (go1_rough with
 an observation history: cfg.history), go1_rough_actrand (go1_rough with per-env drive gains and
 action latency: cfg.actuator_rand), go1_rough_cmdcur (go1_rough with the command curriculum:
-commands.curriculum, lin_vel_x widening from half of go1_rough's range), go1_flat_bench (C2 as
+commands.curriculum, lin_vel_x widening from half of go1_rough's range), go1_rough_sym (go1_rough
+trained with left-right symmetry data augmentation: algorithm.symmetry), go1_flat_bench (C2 as
 BASELINE states it: PD, no domain randomisation), anymal_c_rough (C5), anymal_c_flat, and the
 remaining robots of the reference registry: anymal_b, a1, a1_src, aliengo and cassie (the biped:
 2 legs x 6 joints on the dense physics kernel).
@@ -25,7 +26,8 @@ from .cassie.cassie_config import CassieRoughCfg, CassieRoughCfgPPO
 from .base.legged_robot_config import LeggedRobotCfg, LeggedRobotCfgPPO
 from .go1.go1 import Go1
 from .go1.go1_config import (Go1FlatBenchCfg, Go1RoughActRandCfg, Go1RoughAsymCfg, Go1RoughCfg, Go1RoughCfgPPO,
-                             Go1RoughCmdCurCfg, Go1RoughHistCfg, Go1RoughNormCfgPPO, Go1RoughTerrainCfg)
+                             Go1RoughCmdCurCfg, Go1RoughHistCfg, Go1RoughNormCfgPPO, Go1RoughSymCfgPPO,
+                             Go1RoughTerrainCfg)
 
 task_registry.register("go1", Go1, Go1RoughCfg(), Go1RoughCfgPPO())
 task_registry.register("go1_flat_bench", Go1, Go1FlatBenchCfg(), Go1RoughCfgPPO())
@@ -44,3 +46,5 @@ task_registry.register("cassie", Cassie, CassieRoughCfg(), CassieRoughCfgPPO())
 task_registry.register_variant("go1_rough_asym_norm", "go1_rough_asym", Go1RoughNormCfgPPO())
 # go1_rough with commands.curriculum: the same env class, an env cfg of its own
 task_registry.register_variant("go1_rough_cmdcur", "go1_rough", Go1RoughCfgPPO(), env_cfg=Go1RoughCmdCurCfg())
+# go1_rough trained on its rollout rows and their mirror images: the same env, another train cfg
+task_registry.register_variant("go1_rough_sym", "go1_rough", Go1RoughSymCfgPPO())

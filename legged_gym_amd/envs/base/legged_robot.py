@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from legged_gym_amd import LEGGED_GYM_ROOT_DIR
-from legged_gym_amd.envs.base import actuator_rand, command_curriculum, history, privileged
+from legged_gym_amd.envs.base import actuator_rand, command_curriculum, history, privileged, symmetry
 from legged_gym_amd.envs.base.base_task import BaseTask
 from legged_gym_amd.sim import abi
 from legged_gym_amd.sim.model import RobotAsset, build_model, resolve_asset_path
@@ -757,6 +757,27 @@ class LeggedRobot(BaseTask):
         self._backend.bind_obs_history(self._hist_bufs[self._obs_slot], self._hist_bufs[self._obs_slot ^ 1], layout)
         self.num_obs = layout.width
         self.obs_buf = self._hist_bufs[self._obs_slot]
+
+    def symmetry_tables(self):
+        """The left-right mirror tables of this env's rows (envs/base/symmetry.py): {"obs": env.num_obs
+        wide, "critic_obs": the privileged width or None, "actions"}, each a (perm int32, sign float32)
+        pair of tensors on the env's device with mirror(x)[c] = sign[c] * x[perm[c]].  Built once;
+        ValueError for a robot, height grid, history or default pose that has no mirror image."""
+        if getattr(self, "_symmetry_tables", None) is None:
+            tcfg = self.cfg.terrain
+            measure = bool(tcfg.measure_heights)
+            body_names = self.asset.body_names
+            t = symmetry.env_tables(
+                self.asset.data, self.dof_names, [b["name"] for b in self.asset.data["dyn_bodies"]],
+                [body_names[i] for i in self.feet_indices.cpu().tolist()], self.default_dof_pos[0].cpu().tolist(),
+                self.num_base_obs, tcfg.measured_points_x if measure else (), tcfg.measured_points_y if measure else (),
+                self.privileged_layout, self.history_layout)
+            dev = self.device
+            self._symmetry_tables = {
+                k: None if v is None else (torch.tensor(v[0], dtype=torch.int32, device=dev),
+                                           torch.tensor(v[1], dtype=torch.float32, device=dev))
+                for k, v in t.items()}
+        return self._symmetry_tables
 
     def _trimesh_contact_table(self):
         """mesh_type 'trimesh' with a slope threshold: the contact table of the slope-corrected mesh

@@ -243,6 +243,17 @@ class LeggedRobotCfgPPO(BaseConfig):  # ref :218-255
         desired_kl = 0.01
         max_grad_norm = 1.
 
+        class symmetry:
+            """rsl_rl 2.x symmetry_cfg.  use_data_augmentation = True trains every
+            minibatch on its M rollout rows and their M left-right mirror images (2 M rows, the number
+            of minibatches unchanged); the tables come from the env (LeggedRobot.symmetry_tables(),
+            envs/base/symmetry.py) and the mirror rows are written on the device once per update.
+            Deviation from rsl_rl 2.x: the adaptive schedule's KL is the mean over all 2 M rows (mirror
+            rows carry the mirrored old mu / sigma), where rsl_rl 2.x averages the real half only.  Not
+            supported (ValueError): recurrent policies, runner.empirical_normalization together with
+            it, and any other key here (use_mirror_loss among them).  False: nothing changes."""
+            use_data_augmentation = False
+
     class runner:
         policy_class_name = 'ActorCritic'
         algorithm_class_name = 'PPO'

@@ -11,6 +11,9 @@ go1_rough_hist; `Go1RoughAsymHistCfg` pairs the history with the privileged crit
 registered as go1_rough_actrand.
 `Go1RoughCmdCurCfg` is go1_rough with the command curriculum, registered as
 go1_rough_cmdcur.
+`Go1RoughSymCfgPPO` trains with left-right symmetry data augmentation: go1_rough under
+it is registered as go1_rough_sym; `Go1RoughAsymHistSymCfg` names the widest combination (history actor,
+privileged critic) meant to be trained with it (not registered).
 """
 from legged_gym_amd.envs.base.legged_robot_config import LeggedRobotCfg, LeggedRobotCfgPPO
 
@@ -76,6 +79,14 @@ class Go1RoughNormCfgPPO(Go1RoughCfgPPO):
     """Go1RoughCfgPPO with empirical observation normalisation in front of the actor and the critic."""
     class runner(Go1RoughCfgPPO.runner):
         empirical_normalization = True
+
+
+class Go1RoughSymCfgPPO(Go1RoughCfgPPO):
+    """Go1RoughCfgPPO with symmetry data augmentation: every minibatch holds its rollout rows and
+    their mirror images (rsl_rl 2.x symmetry_cfg.use_data_augmentation)."""
+    class algorithm(Go1RoughCfgPPO.algorithm):
+        class symmetry(Go1RoughCfgPPO.algorithm.symmetry):
+            use_data_augmentation = True
 
 
 class Go1FlatBenchCfg(Go1RoughCfg):
@@ -153,3 +164,10 @@ class Go1RoughAsymHistCfg(Go1RoughAsymCfg):
     Go1RoughCfgPPO())."""
     class history(Go1RoughAsymCfg.history):
         frames = 5
+
+
+class Go1RoughAsymHistSymCfg(Go1RoughAsymHistCfg):
+    """go1_rough with the 475-wide history row for the actor and the 253-wide privileged row for the
+    critic, to be trained under Go1RoughSymCfgPPO: all three mirror tables (history frames, privileged
+    tail, actions) are in use.  Not in the registry: task_registry.register(name, Go1,
+    Go1RoughAsymHistSymCfg(), Go1RoughSymCfgPPO())."""

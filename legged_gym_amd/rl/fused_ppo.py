@@ -242,6 +242,7 @@ class FusedPPOUpdate:
     _t_period = _t_count = _t_mb = 0             # time_gemms()
     _t_events = _c_events = ()
     Xall = Xall2 = Xcall = None                  # _gather_all's buffers
+    time_augment, augment_events = False, ()     # tools/train_time.py: event pairs around each augment launch
     _rec_idx = _mem_ctx = None                   # recurrent minibatches
 
     @staticmethod
@@ -633,8 +634,14 @@ class FusedPPOUpdate:
         t_issue = time.perf_counter()
         ppo = self.ppo
         nmb = ppo.num_mini_batches
-        M = ppo.storage.num_transitions_per_env * ppo.storage.num_envs // nmb
-        stream = self._begin_update(M)
+        B = ppo.storage.num_transitions_per_env * ppo.storage.num_envs
+        M = B // nmb
+        # symmetry augmentation: M real rows + their M mirrors per minibatch through the same kernels
+        sym = ppo.storage.symmetry is not None
+        Mr = 2 * M if sym else M
+        stream = self._begin_update(Mr)
+        if sym:
+            self.augment(stream)
         # rsl_rl's permutation, drawn on a second stream (the generator's offset is taken at issue:
         # the same permutation on any stream): its sort chain of small launches runs next to the
         # rollout's last steps / GAE still queued on this stream instead of after them
@@ -645,15 +652,17 @@ class FusedPPOUpdate:
             indices = torch.randperm(nmb * M, requires_grad=False, device=self.dev)
         main.wait_stream(self._perm_stream)
         indices.record_stream(main)
+        if sym:   # minibatch i: perm[iM:(i+1)M], then the same rows' mirrors (row B + r mirrors row r)
+            indices = torch.stack((indices.view(nmb, M), indices.view(nmb, M) + B), 1).reshape(-1)
         obs, cobs, storage = self._storage_views()
         args = self._loss_args(storage)
         # rsl_rl draws ONE permutation per update and every epoch walks the same minibatches, so
         # the padded layer-1 inputs are gathered once (one launch over all rows) and a minibatch
         # reads its contiguous slice: no per-minibatch gather
-        xs = self._gather_all(indices, obs, cobs, nmb * M, stream) if self.lgx_gemm else [None] * nmb
+        xs = self._gather_all(indices, obs, cobs, nmb * Mr, stream) if self.lgx_gemm else [None] * nmb
         for _ in range(ppo.num_learning_epochs):
             for i in range(nmb):
-                self._minibatch(indices[i * M:(i + 1) * M], obs, cobs, args, stream, xs=xs[i])
+                self._minibatch(indices[i * Mr:(i + 1) * Mr], obs, cobs, args, stream, xs=xs[i])
         self.host_issue_s = time.perf_counter() - t_issue   # host time to issue every launch (tools/host_overhead.py)
         return self._finish(ppo.num_learning_epochs * nmb, defer)
 
@@ -678,15 +687,47 @@ class FusedPPOUpdate:
 
     def _storage_views(self):
         """(obs, privileged obs or None, the loss kernel's seven storage arrays), flat over the
-        T x N transitions."""
+        T x N transitions - with symmetry augmentation over 2 T x N rows: the transitions, then their
+        mirror images (augment())."""
         st = self.ppo.storage
+        B = st.num_transitions_per_env * st.num_envs * (2 if st.symmetry is not None else 1)
+        obs = st.full("observations").view(B, -1)
+        cobs = st.full("privileged_observations").view(B, -1) if st.privileged_observations is not None else None
+        return obs, cobs, dict(actions=st.full("actions").view(B, -1), old_logp=st.full("actions_log_prob").view(B),
+                               old_mu=st.full("mu").view(B, -1), old_sigma=st.full("sigma").view(B, -1),
+                               advantages=st.full("advantages").view(B), target_values=st.full("values").view(B),
+                               returns=st.full("returns").view(B))
+
+    def augment(self, stream=None, src_row=0, dst_row=None):
+        """lgx_ppo_symmetry_augment on the storage: rows [dst_row, dst_row + B) of every array a
+        minibatch reads written from rows [src_row, src_row + B) through the storage's mirror tables
+        (B = T x N; by default the mirror half from the real half, once per update)."""
+        st = self.ppo.storage
+        if st.symmetry is None:
+            raise ValueError("augment(): the storage has no symmetry tables")
+        if stream is None:
+            stream = C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
         B = st.num_transitions_per_env * st.num_envs
-        obs = st.observations.view(B, -1)
-        cobs = st.privileged_observations.view(B, -1) if st.privileged_observations is not None else None
-        return obs, cobs, dict(actions=st.actions.view(B, -1), old_logp=st.actions_log_prob.view(B),
-                               old_mu=st.mu.view(B, -1), old_sigma=st.sigma.view(B, -1),
-                               advantages=st.advantages.view(B), target_values=st.values.view(B),
-                               returns=st.returns.view(B))
+        a = abi.LgxSymmetryArgs()
+        a.rows, a.src_row, a.dst_row = B, src_row, B if dst_row is None else dst_row
+        a.num_obs, a.num_actions = st.full("observations").shape[-1], st.full("actions").shape[-1]
+        for name in ("observations", "actions", "mu", "sigma", "actions_log_prob", "advantages", "values", "returns"):
+            setattr(a, name, st.full(name).data_ptr())
+        tab = st.symmetry
+        a.obs_perm, a.obs_sign = tab["obs"][0].data_ptr(), tab["obs"][1].data_ptr()
+        a.act_perm, a.act_sign = tab["actions"][0].data_ptr(), tab["actions"][1].data_ptr()
+        if st.privileged_observations is not None:
+            a.num_cobs = st.full("privileged_observations").shape[-1]
+            a.privileged_observations = st.full("privileged_observations").data_ptr()
+            a.cobs_perm, a.cobs_sign = tab["critic_obs"][0].data_ptr(), tab["critic_obs"][1].data_ptr()
+        ev = None
+        if self.time_augment:   # (tools/train_time.py: the launch's own time, read after the run)
+            ev = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            ev[0].record()
+        self.check(self.lib.lgx_ppo_symmetry_augment(C.byref(a), stream), "lgx_ppo_symmetry_augment")
+        if ev:
+            ev[1].record()
+            self.augment_events = (*self.augment_events, ev)
 
     def _finish(self, n, defer):
         """The update's readback (statistics, adapted learning rate) over its n minibatches: now, or

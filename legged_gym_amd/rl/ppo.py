@@ -33,13 +33,37 @@ def _dist():
     return dist if dist.is_available() and dist.is_initialized() and dist.get_world_size() >= least else None
 
 
+def _symmetry_on(cfg):
+    """algorithm.symmetry (None, a dict or a config object) -> whether data augmentation is on;
+    ValueError for the mirror loss or any key this implementation does not know."""
+    if cfg is None:
+        return False
+    d = dict(cfg) if isinstance(cfg, dict) else {k: getattr(cfg, k) for k in dir(cfg) if not k.startswith("_")}
+    unknown = sorted(set(d) - {"use_data_augmentation"})
+    if unknown:
+        raise ValueError(f"symmetry: unsupported key(s) {unknown} (only use_data_augmentation is implemented; the "
+                         "mirror loss is not)")
+    return bool(d.get("use_data_augmentation", False))
+
+
 class PPO:
     actor_critic: ActorCritic
 
     def __init__(self, actor_critic, num_learning_epochs=1, num_mini_batches=1, clip_param=0.2, gamma=0.998, lam=0.95,
                  value_loss_coef=1.0, entropy_coef=0.0, learning_rate=1e-3, max_grad_norm=1.0,
-                 use_clipped_value_loss=True, schedule="fixed", desired_kl=0.01, device="cpu", use_fused_update=True):
+                 use_clipped_value_loss=True, schedule="fixed", desired_kl=0.01, device="cpu", use_fused_update=True,
+                 symmetry=None):
+        """symmetry: None, or the `algorithm.symmetry` config as a dict (class_to_dict) or an object with
+        attributes.  use_data_augmentation = True trains every minibatch on its rollout rows and their
+        left-right mirror images (rsl_rl 2.x symmetry_cfg.use_data_augmentation): the
+        caller then hands the env's tables to init_symmetry() before init_storage().  Off, None and
+        absent all mean nothing changes."""
         self.device = device
+        self.symmetry = _symmetry_on(symmetry)
+        self.symmetry_tables = None
+        if self.symmetry and actor_critic.is_recurrent:
+            raise ValueError("symmetry.use_data_augmentation: recurrent policies are not supported (a mirrored "
+                             "trajectory needs its own memory states)")
         self.desired_kl = desired_kl
         self.schedule = schedule
         self.learning_rate = learning_rate
@@ -71,8 +95,38 @@ class PPO:
 
     # ---------------------------------------------------------------- setup / modes
     def init_storage(self, num_envs, num_transitions_per_env, actor_obs_shape, critic_obs_shape, action_shape):
+        if self.symmetry and self.symmetry_tables is None:
+            raise ValueError("symmetry.use_data_augmentation is on: call init_symmetry(env.symmetry_tables()) "
+                             "before init_storage()")
+        if self.symmetry:
+            for key, shape in (("obs", actor_obs_shape), ("critic_obs", critic_obs_shape), ("actions", action_shape)):
+                t = self.symmetry_tables[key]
+                if (t is None) != (shape[0] is None) or (t is not None and t[0].numel() != shape[0]):
+                    raise ValueError(f"symmetry: the {key} table is {None if t is None else t[0].numel()} wide, the "
+                                     f"storage's rows {shape[0]}")
         self.storage = RolloutStorage(num_envs, num_transitions_per_env, actor_obs_shape, critic_obs_shape,
-                                      action_shape, self.device)
+                                      action_shape, self.device, symmetry=self.symmetry_tables)
+
+    def init_symmetry(self, tables):
+        """The env's mirror tables (LeggedRobot.symmetry_tables(): {"obs", "critic_obs" or None,
+        "actions"} -> (perm int32, sign float32)), moved to this algorithm's device and checked once
+        (every perm entry in range, every sign +-1); ValueError with symmetry off."""
+        if not self.symmetry:
+            raise ValueError("init_symmetry: symmetry.use_data_augmentation is off")
+        tables = {k: None if v is None else (v[0].to(self.device, torch.int32).contiguous(),
+                                             v[1].to(self.device, torch.float32).contiguous())
+                  for k, v in tables.items()}
+        for key, t in tables.items():
+            if t is None:
+                continue
+            perm, sign = t[0].cpu(), t[1].cpu()
+            if self._fused is not None:   # the library's own check of what its launch will trust
+                self._fused.check(self._fused.lib.lgx_ppo_symmetry_check_table(
+                    C.c_void_p(perm.data_ptr()), C.c_void_p(sign.data_ptr()), perm.numel()), "symmetry_check_table")
+            elif (perm.numel() != sign.numel() or not ((perm >= 0) & (perm < perm.numel())).all()
+                  or not (sign.abs() == 1).all()):
+                raise ValueError(f"symmetry: the {key} table is not a signed permutation")
+        self.symmetry_tables = tables
 
     def test_mode(self):
         self.actor_critic.test()

@@ -41,6 +41,11 @@ class OnPolicyRunner:
         actor_critic = ac_class(self.env.num_obs, num_critic_obs, self.env.num_actions, **self.policy_cfg).to(self.device)
         alg_class = {"PPO": PPO}[self.cfg["algorithm_class_name"]]
         self.alg = alg_class(actor_critic, device=self.device, **self.alg_cfg)
+        if getattr(self.alg, "symmetry", False):   # algorithm.symmetry.use_data_augmentation
+            if self.cfg.get("empirical_normalization", False):
+                raise ValueError("symmetry.use_data_augmentation with runner.empirical_normalization: the storage "
+                                 "holds normalised rows, and per-column statistics are not mirror-symmetric")
+            self.alg.init_symmetry(self.env.symmetry_tables())
         self.num_steps_per_env = self.cfg["num_steps_per_env"]
         self.save_interval = self.cfg["save_interval"]
         self.alg.init_storage(self.env.num_envs, self.num_steps_per_env, [self.env.num_obs],

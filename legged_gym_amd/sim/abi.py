@@ -178,7 +178,15 @@ class LgxObsNormJob(C.Structure):   # lgx_obs_norm_job (rl/normalizer.py)
                 ("eps", C.c_double)]
 
 
-OBS_NORM_ROWS = 64        # LGX_OBS_NORM_ROWS (checked against lgx_obs_norm_rows_per_part at first use)
+class LgxSymmetryArgs(C.Structure):   # lgx_symmetry_args (the tables: envs/base/symmetry.py)
+    _fields_ = [("rows", i64), ("src_row", i64), ("dst_row", i64),
+                ("num_obs", i32), ("num_cobs", i32), ("num_actions", i32), ("pad", i32)] + [
+        (n, C.c_void_p) for n in ("observations", "privileged_observations", "actions", "mu", "sigma",
+                                  "actions_log_prob", "advantages", "values", "returns", "obs_perm", "obs_sign",
+                                  "cobs_perm", "cobs_sign", "act_perm", "act_sign")]
+
+
+OBS_NORM_ROWS = 64       # LGX_OBS_NORM_ROWS (checked against lgx_obs_norm_rows_per_part at first use)
 OBS_NORM_MAX_JOBS = 2     # LGX_OBS_NORM_MAX_JOBS
 PPO_MAX_ACTIONS = 16
 MAX_REDUCE_JOBS = 16
@@ -292,6 +300,8 @@ def declare(lib, prefix="lgx"):
             "obs_norm_part_doubles": (i64, [i64, i32]),
             "obs_norm_partials": (C.c_int, [C.POINTER(LgxObsNormJob), i32, vp]),
             "obs_norm_apply": (C.c_int, [C.POINTER(LgxObsNormJob), i32, vp]),
+            "ppo_symmetry_augment": (C.c_int, [C.POINTER(LgxSymmetryArgs), vp]),
+            "ppo_symmetry_check_table": (C.c_int, [vp, vp, i32]),
         })
     for name, (res, args) in sigs.items():
         fn = getattr(lib, f"{prefix}_{name}")
@@ -314,7 +324,8 @@ EXPORTED = ["lgx_last_error", "lgx_version", "lgx_physics_lane_split", "lgx_trim
             "lgx_launch_bind_event", "lgx_launch_bind_pending",
             "lgx_comm_unique_id", "lgx_comm_create", "lgx_comm_destroy", "lgx_allreduce_grads",
             "lgx_episode_stats_step",
-            "lgx_obs_norm_rows_per_part", "lgx_obs_norm_part_doubles", "lgx_obs_norm_partials", "lgx_obs_norm_apply"]
+            "lgx_obs_norm_rows_per_part", "lgx_obs_norm_part_doubles", "lgx_obs_norm_partials", "lgx_obs_norm_apply",
+            "lgx_ppo_symmetry_augment", "lgx_ppo_symmetry_check_table"]
 
 
 def check_layout(sizes_fn, n=12):

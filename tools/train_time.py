@@ -12,7 +12,9 @@ Configurations (one runner with a temporary log directory, one without, on one e
 A window is one learn(iters) between two device synchronisations, its stdout discarded; with a
 log directory it contains the checkpoints learn() writes (every save_interval iterations and at
 its end).  The windows of the configurations alternate, after learn(warmup) of each.  Prints one
-JSON line: per configuration the median ms per iteration and every window's.
+JSON line: per configuration the median ms per iteration and every window's, the last iteration's
+collection / learn phases, and for a task with symmetry augmentation (go1_rough_sym) the augment
+launch's time from HIP events around it.
 """
 import argparse
 import contextlib
@@ -57,6 +59,12 @@ def main():
             runners[logged], _ = task_registry.make_alg_runner(env, name=task, args=cli, train_cfg=train_cfg,
                                                                log_root=tmp if logged else None)
 
+        # symmetry augmentation (algorithm.symmetry): HIP events around each update's augment launch
+        fused = [r.alg._fused for r in runners.values()
+                 if getattr(r.alg, "_fused", None) is not None and r.alg.storage.symmetry is not None]
+        for f in fused:
+            f.time_augment = True
+
         def learn(config, n):
             for k in ("LGX_DEVICE_STATS", "LGX_DEFER_LOG"):
                 os.environ.pop(k, None)
@@ -72,10 +80,18 @@ def main():
         for _ in range(a.windows):
             for c in configs:
                 out[c].append(round(learn(c, a.iters), 4))
-    print(json.dumps({"task": task, "num_envs": a.num_envs, "iters_per_window": a.iters, "warmup_iters": a.warmup,
-                      "device": torch.cuda.get_device_name(0),
-                      "ms_per_iteration": {c: {"median": round(statistics.median(w), 4), "windows": w}
-                                           for c, w in out.items()}}), flush=True)
+        # the last iteration's phases (the runner's stream events) and every augment launch's time
+        phases = {("logged" if logged else "unlogged"): {k: round(r.last_iteration_stats[k] * 1e3, 4)
+                                                         for k in ("collection_time", "learn_time")}
+                  for logged, r in runners.items()}
+        augment = [e0.elapsed_time(e1) * 1e3 for f in fused for e0, e1 in f.augment_events]
+    res = {"task": task, "num_envs": a.num_envs, "iters_per_window": a.iters, "warmup_iters": a.warmup,
+           "device": torch.cuda.get_device_name(0),
+           "ms_per_iteration": {c: {"median": round(statistics.median(w), 4), "windows": w} for c, w in out.items()},
+           "last_iteration_phases_ms": phases}
+    if augment:
+        res["augment_us"] = {"median": round(statistics.median(augment), 2), "launches": len(augment)}
+    print(json.dumps(res), flush=True)
 
 
 if __name__ == "__main__":
