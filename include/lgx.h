@@ -439,8 +439,6 @@ typedef struct lgx_cmd_curriculum_desc {
   float* state;
 } lgx_cmd_curriculum_desc;
 int lgx_bind_command_curriculum(lgx_sim* sim, const lgx_cmd_curriculum_desc* desc);
-/* sizeof(lgx_cmd_curriculum_desc) and the offsets of max_curriculum, threshold, state */
-void lgx_cmd_curriculum_desc_layout(int64_t out[4]);
 /* The host's test for a curriculum step: common_step_counter % max_episode_length == 0 with the
  * integer-valued float length of lgx_env_params (counter 0 included); 0 for a length <= 0. */
 int32_t lgx_is_curriculum_step(int64_t common_step_counter, float max_episode_length);

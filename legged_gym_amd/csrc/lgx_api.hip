@@ -71,6 +71,30 @@ static hipEvent_t take_event(lgx_sim* s) {
 }
 thread_local lgx_timing_slot lgx_timing;
 
+// Library-owned device scratch of a sim (hist.age, arand.prev, ccur.changed): allocated by the first
+// bind, kept by later ones, zeroed by every one - a (re)bind starts without a past.  A setup call: the
+// device is drained before and after the memset, so it is ordered against launches on any stream.
+// `who` (the entry point) and `what` (the buffer) name the failing call in lgx_last_error; a buffer
+// this call allocated is released again when it fails.
+static int scratch_zeroed(void** slot, size_t bytes, const char* who, const char* what) {
+  const std::string w(who), of = std::string("(") + what + ")";
+  const bool fresh = !*slot;
+  int rc = fresh ? hip_check(hipMalloc(slot, bytes), (w + ": hipMalloc" + of).c_str()) : 0;
+  if (!rc) rc = hip_check(hipDeviceSynchronize(), (w + ": hipDeviceSynchronize").c_str());
+  if (!rc) rc = hip_check(hipMemset(*slot, 0, bytes), (w + ": hipMemset" + of).c_str());
+  if (!rc) rc = hip_check(hipDeviceSynchronize(), (w + ": hipDeviceSynchronize").c_str());
+  if (rc && fresh && *slot) {
+    (void)hipFree(*slot);
+    *slot = nullptr;
+  }
+  return rc;
+}
+static int scratch_release(void** slot, const char* who, const char* what) {
+  const int rc = *slot ? hip_check(hipFree(*slot), (std::string(who) + ": hipFree(" + what + ")").c_str()) : 0;
+  *slot = nullptr;
+  return rc;
+}
+
 // arm the kernel-tight event pair for the next launch of kernel class `cls` (see LGX_LAUNCH)
 static void arm(lgx_sim* s, int cls, bool sample) {
   lgx_timing = lgx_timing_slot{};
@@ -244,9 +268,9 @@ int lgx_sim_destroy(lgx_sim* s) {
   }
   for (auto& v : s->ev) for (hipEvent_t e : v) (void)hipEventDestroy(e);
   for (hipEvent_t e : s->pool) (void)hipEventDestroy(e);
-  (void)hipFree(s->hist.age);
-  (void)hipFree(s->arand.prev);
-  (void)hipFree(s->ccur.changed);
+  (void)scratch_release((void**)&s->hist.age, "lgx_sim_destroy", "age");
+  (void)scratch_release((void**)&s->arand.prev, "lgx_sim_destroy", "prev");
+  (void)scratch_release((void**)&s->ccur.changed, "lgx_sim_destroy", "changed");
   (void)hipFree(s->d_model);
   (void)hipFree(s->d_params);
   delete s;
@@ -368,7 +392,7 @@ int lgx_rebind_privileged_obs(lgx_sim* s, float* buf) {
 int lgx_bind_obs_history(lgx_sim* s, float* row, const float* prev, const lgx_obs_history_desc* d) {
   if (!s) return fail(LGX_EINVAL, "lgx_bind_obs_history: null sim");
   if (!row) {
-    int rc = s->hist.age ? hip_check(hipFree(s->hist.age), "lgx_bind_obs_history: hipFree(age)") : 0;
+    int rc = scratch_release((void**)&s->hist.age, "lgx_bind_obs_history", "age");
     s->hist = lgx_hist_args{};
     return rc;
   }
@@ -382,18 +406,11 @@ int lgx_bind_obs_history(lgx_sim* s, float* row, const float* prev, const lgx_ob
   if ((int64_t)d->width != (int64_t)p.num_obs + (int64_t)d->frames * d->frame_width)
     return fail(LGX_EINVAL, "lgx_bind_obs_history: width is not num_obs + frames * frame_width");
   if (d->width > LGX_MAX_PRIV_OBS) return fail(LGX_EINVAL, "lgx_bind_obs_history: width is above LGX_MAX_PRIV_OBS");
-  // a (re)bind starts every env without a past: allocate once, zero every time.  A setup call: the
-  // device is drained before and after the memset, so it is ordered against launches on any stream
-  int32_t* age = s->hist.age;
-  if (!age) {
-    if (int rc = hip_check(hipMalloc(&age, sizeof(int32_t) * (size_t)p.num_envs), "lgx_bind_obs_history: hipMalloc(age)"))
-      return rc;
-  }
-  s->hist = lgx_hist_args{row, prev, age, d->frames, d->frame_width, d->width};
-  if (int rc = hip_check(hipDeviceSynchronize(), "lgx_bind_obs_history: hipDeviceSynchronize")) return rc;
-  if (int rc = hip_check(hipMemset(age, 0, sizeof(int32_t) * (size_t)p.num_envs), "lgx_bind_obs_history: hipMemset(age)"))
+  // a (re)bind starts every env without a past
+  if (int rc = scratch_zeroed((void**)&s->hist.age, sizeof(int32_t) * (size_t)p.num_envs, "lgx_bind_obs_history", "age"))
     return rc;
-  return hip_check(hipDeviceSynchronize(), "lgx_bind_obs_history: hipDeviceSynchronize");
+  s->hist = lgx_hist_args{row, prev, s->hist.age, d->frames, d->frame_width, d->width};
+  return 0;
 }
 
 int lgx_rebind_obs_history(lgx_sim* s, float* row, const float* prev) {
@@ -408,7 +425,7 @@ int lgx_rebind_obs_history(lgx_sim* s, float* row, const float* prev) {
 int lgx_bind_actuator_rand(lgx_sim* s, const lgx_actuator_rand_desc* d) {
   if (!s) return fail(LGX_EINVAL, "lgx_bind_actuator_rand: null sim");
   if (!d || (!d->kp_scale && !d->kd_scale && !d->lag)) {
-    int rc = s->arand.prev ? hip_check(hipFree(s->arand.prev), "lgx_bind_actuator_rand: hipFree(prev)") : 0;
+    int rc = scratch_release((void**)&s->arand.prev, "lgx_bind_actuator_rand", "prev");
     s->arand = lgx_act_rand_args{};
     return rc;
   }
@@ -417,24 +434,12 @@ int lgx_bind_actuator_rand(lgx_sim* s, const lgx_actuator_rand_desc* d) {
   if (ctrl == LGX_CTRL_SEA) return fail(LGX_EINVAL, "lgx_bind_actuator_rand: LGX_CTRL_SEA has no actuator tables");
   if (ctrl == LGX_CTRL_T && (d->kp_scale || d->kd_scale))
     return fail(LGX_EINVAL, "lgx_bind_actuator_rand: LGX_CTRL_T has no gains to scale");
-  // a (re)bind starts every env without an earlier action: allocate once, zero every time.  A setup
-  // call: the device is drained before and after the memset, so it is ordered against launches on any stream
-  const size_t bytes = sizeof(float) * (size_t)s->params.num_envs * LGX_NUM_DOF;
-  float* prev = s->arand.prev;
-  if (!prev) {
-    if (int rc = hip_check(hipMalloc(&prev, bytes), "lgx_bind_actuator_rand: hipMalloc(prev)")) return rc;
-  }
-  s->arand = lgx_act_rand_args{d->kp_scale, d->kd_scale, d->lag, prev};
-  if (int rc = hip_check(hipDeviceSynchronize(), "lgx_bind_actuator_rand: hipDeviceSynchronize")) return rc;
-  if (int rc = hip_check(hipMemset(prev, 0, bytes), "lgx_bind_actuator_rand: hipMemset(prev)")) return rc;
-  return hip_check(hipDeviceSynchronize(), "lgx_bind_actuator_rand: hipDeviceSynchronize");
-}
-
-void lgx_cmd_curriculum_desc_layout(int64_t out[4]) {
-  out[0] = (int64_t)sizeof(lgx_cmd_curriculum_desc);
-  out[1] = (int64_t)offsetof(lgx_cmd_curriculum_desc, max_curriculum);
-  out[2] = (int64_t)offsetof(lgx_cmd_curriculum_desc, threshold);
-  out[3] = (int64_t)offsetof(lgx_cmd_curriculum_desc, state);
+  // a (re)bind starts every env without an earlier action
+  if (int rc = scratch_zeroed((void**)&s->arand.prev, sizeof(float) * (size_t)s->params.num_envs * LGX_NUM_DOF,
+                              "lgx_bind_actuator_rand", "prev"))
+    return rc;
+  s->arand = lgx_act_rand_args{d->kp_scale, d->kd_scale, d->lag, s->arand.prev};
+  return 0;
 }
 
 // common_step_counter % max_episode_length == 0 with an integer-valued float length (legged_robot.py:165)
@@ -446,7 +451,7 @@ int32_t lgx_is_curriculum_step(int64_t common_step_counter, float max_episode_le
 int lgx_bind_command_curriculum(lgx_sim* s, const lgx_cmd_curriculum_desc* d) {
   if (!s) return fail(LGX_EINVAL, "lgx_bind_command_curriculum: null sim");
   if (!d) {
-    int rc = s->ccur.changed ? hip_check(hipFree(s->ccur.changed), "lgx_bind_command_curriculum: hipFree(changed)") : 0;
+    int rc = scratch_release((void**)&s->ccur.changed, "lgx_bind_command_curriculum", "changed");
     s->ccur = lgx_cmdcur_args{};
     return rc;
   }
@@ -464,14 +469,10 @@ int lgx_bind_command_curriculum(lgx_sim* s, const lgx_cmd_curriculum_desc* d) {
   for (int i = 9; i < 12; ++i)
     if (p.noise_scale_vec[i] != 0.f)
       return fail(LGX_EINVAL, "lgx_bind_command_curriculum: the command columns (9..11) of noise_scale_vec must be zero");
-  // a setup call, ordered against launches on any stream by draining the device (as lgx_bind_actuator_rand)
-  int32_t* changed = s->ccur.changed;
-  if (!changed) {
-    if (int rc = hip_check(hipMalloc(&changed, sizeof(int32_t)), "lgx_bind_command_curriculum: hipMalloc(changed)")) return rc;
-  }
-  s->ccur = lgx_cmdcur_args{d->state, changed, d->max_curriculum, d->threshold, row};
-  if (int rc = hip_check(hipDeviceSynchronize(), "lgx_bind_command_curriculum: hipDeviceSynchronize")) return rc;
-  if (int rc = hip_check(hipMemset(changed, 0, sizeof(int32_t)), "lgx_bind_command_curriculum: hipMemset(changed)")) return rc;
+  if (int rc = scratch_zeroed((void**)&s->ccur.changed, sizeof(int32_t), "lgx_bind_command_curriculum", "changed"))
+    return rc;
+  s->ccur = lgx_cmdcur_args{d->state, s->ccur.changed, d->max_curriculum, d->threshold, row};
+  // the state's first values, then drained like the scratch: ordered against launches on any stream
   if (int rc = launch_check(lgx_launch_cmd_curriculum_init(s->d_params, d->state, nullptr),
                             "lgx_bind_command_curriculum: launch"))
     return rc;
@@ -568,9 +569,8 @@ int lgx_ground_contact(lgx_sim* s, const float* points, int32_t n, float* out, v
 
 int lgx_post_physics(lgx_sim* s, int64_t step, void* stream) {
   if (!s) return fail(LGX_EINVAL, "lgx_post_physics: null sim");
-  if (int rc = launch_check(lgx_launch_post_physics(s->d_params, s->bufs, s->params.num_envs, s->params.num_obs,
-                                                    s->n_term_rows, s->params.measure_heights, step, s->draws,
-                                                    s->extras_snapshot, s->priv, s->hist, (hipStream_t)stream),
+  if (int rc = launch_check(lgx_launch_post_physics(s->d_params, s->bufs, s->params.num_envs, step, s->draws,
+                                                    s->extras_snapshot, nullptr, s->priv, s->hist, (hipStream_t)stream),
                             "lgx_post_physics: launch"))
     return rc;
   return command_curriculum(s, step, (hipStream_t)stream, nullptr, 0);
@@ -606,10 +606,10 @@ static int post_physics_fused(lgx_sim* s, int64_t step, hipStream_t st, bool sam
     // UniNet on every (substep, env, leg) row of this step's model_ins, inside the post-physics
     // launch (the next physics launch, stream-ordered after it, rewrites model_ins)
     arm(s, 2, sample);
-    rc = launch_check(lgx_launch_post_physics_act(s->d_params, s->bufs, p.num_envs, step, s->draws, s->extras_snapshot,
-                                                  s->bufs.model_ins, s->bufs.act_dvel,
-                                                  (int64_t)p.decimation * p.num_envs * 4, s->bufs.act_net_w,
-                                                  s->bufs.act_net_scale, s->priv, s->hist, st),
+    const lgx_act_launch act{s->bufs.model_ins, s->bufs.act_dvel, (int64_t)p.decimation * p.num_envs * 4,
+                             s->bufs.act_net_w, s->bufs.act_net_scale};
+    rc = launch_check(lgx_launch_post_physics(s->d_params, s->bufs, p.num_envs, step, s->draws, s->extras_snapshot, &act,
+                                              s->priv, s->hist, st),
                       "lgx_step: post-physics + actuator launch");
     lgx_timing = lgx_timing_slot{};
     return rc ? rc : command_curriculum(s, step, st, nullptr, 0);
@@ -684,9 +684,8 @@ int lgx_profile_collect(lgx_sim* s, double* ms, int64_t* count) {
 int lgx_reset_idx(lgx_sim* s, const int32_t* env_ids, int32_t n, int64_t step, int32_t init_done, void* stream) {
   if (!s || n < 0 || (n > 0 && !env_ids)) return fail(LGX_EINVAL, "lgx_reset_idx: bad arguments");
   if (n > s->params.num_envs) return fail(LGX_EINVAL, "lgx_reset_idx: more ids than envs");
-  if (int rc = launch_check(lgx_launch_reset_idx(s->d_params, s->bufs, s->params.num_envs, s->n_term_rows, env_ids, n,
-                                                 step, init_done, s->draws, s->extras_snapshot, s->hist.age,
-                                                 (hipStream_t)stream),
+  if (int rc = launch_check(lgx_launch_reset_idx(s->d_params, s->bufs, env_ids, n, step, init_done, s->draws,
+                                                 s->extras_snapshot, s->hist.age, (hipStream_t)stream),
                             "lgx_reset_idx: launch"))
     return rc;
   return n > 0 ? command_curriculum(s, step, (hipStream_t)stream, env_ids, n) : 0;

@@ -706,7 +706,7 @@ int actuator_workgroups(int64_t act_rows) {
 
 // This file is compiled twice.  On its own it gives the kernels of a sim without an observation
 // history; lgx_envlogic_hist.hip includes it with LGX_ENVLOGIC_HIST defined and gives the history
-// instantiations and their launchers, nothing else.  They are kept out of this translation unit
+// instantiations and the launcher's choice among them, nothing else.  They are kept out of this translation unit
 // because instantiations compiled together perturb each other's code generation (with them here the
 // privileged kernels came out with the operands of one integer add swapped), and the kernels
 // launched with no history bound are meant to stay the machine code they were (tools/kernel_code_diff.py).
@@ -780,46 +780,34 @@ lgx_extras_finalize_kernel(const lgx_env_params* __restrict__ P, lgx_buffers B, 
   extras_finalize_body(P, B, nblocks, level_scan, snapshot, 256);
 }
 
-int lgx_launch_post_physics(const lgx_env_params* dp, const lgx_buffers& b, int32_t n_envs, int32_t num_obs,
-                            int32_t n_term_rows, int32_t measure_heights, int64_t step, const float* draws,
-                            float* extras_snapshot, const lgx_priv_args& pv, const lgx_hist_args& hv,
-                            hipStream_t stream) {
-  (void)num_obs; (void)n_term_rows; (void)measure_heights;
-  if (hv.row) return lgx_launch_post_physics_hist(dp, b, n_envs, step, draws, extras_snapshot, pv, hv, stream);
-  int blocks = (n_envs + LGX_ENV_BLOCK - 1) / LGX_ENV_BLOCK;
-  if (pv.buf)
+int lgx_launch_post_physics(const lgx_env_params* dp, const lgx_buffers& b, int32_t n_envs, int64_t step,
+                            const float* draws, float* extras_snapshot, const lgx_act_launch* act,
+                            const lgx_priv_args& pv, const lgx_hist_args& hv, hipStream_t stream) {
+  static_assert(ENV_THREADS == 256, "the actuator-net workgroups are 256 threads");
+  if (hv.row) return lgx_post_physics_hist_select(dp, b, n_envs, step, draws, extras_snapshot, act, pv, hv, stream);
+  const int blocks = (n_envs + LGX_ENV_BLOCK - 1) / LGX_ENV_BLOCK;
+  if (act) {
+    const int act_wgs = actuator_workgroups(act->rows);
+    WsArgs wa{act->in, act->out, act->rows, act->w, act->scale};
+    if (pv.buf)
+      LGX_LAUNCH(lgx_post_physics_act_priv_kernel, dim3(blocks + act_wgs), dim3(ENV_THREADS), 0, stream, dp, b, step,
+                 draws, extras_snapshot, wa, blocks, pv);
+    else
+      LGX_LAUNCH(lgx_post_physics_act_kernel, dim3(blocks + act_wgs), dim3(ENV_THREADS), 0, stream, dp, b, step, draws,
+                 extras_snapshot, wa, blocks);
+  } else if (pv.buf) {
     LGX_LAUNCH(lgx_post_physics_priv_kernel, dim3(blocks), dim3(ENV_THREADS), 0, stream, dp, b, step, draws,
                extras_snapshot, pv);
-  else
+  } else {
     LGX_LAUNCH(lgx_post_physics_kernel, dim3(blocks), dim3(ENV_THREADS), 0, stream, dp, b, step, draws,
                extras_snapshot);
+  }
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
-int lgx_launch_post_physics_act(const lgx_env_params* dp, const lgx_buffers& b, int32_t n_envs, int64_t step,
-                                const float* draws, float* extras_snapshot, const float* act_in, float* act_out,
-                                int64_t act_rows, const float* act_w, const float* act_scale,
-                                const lgx_priv_args& pv, const lgx_hist_args& hv, hipStream_t stream) {
-  static_assert(ENV_THREADS == 256, "the actuator-net workgroups are 256 threads");
-  if (hv.row)
-    return lgx_launch_post_physics_act_hist(dp, b, n_envs, step, draws, extras_snapshot, act_in, act_out, act_rows,
-                                            act_w, act_scale, pv, hv, stream);
-  const int blocks = (n_envs + LGX_ENV_BLOCK - 1) / LGX_ENV_BLOCK;
-  const int act_wgs = actuator_workgroups(act_rows);
-  WsArgs wa{act_in, act_out, act_rows, act_w, act_scale};
-  if (pv.buf)
-    LGX_LAUNCH(lgx_post_physics_act_priv_kernel, dim3(blocks + act_wgs), dim3(ENV_THREADS), 0, stream, dp, b, step,
-               draws, extras_snapshot, wa, blocks, pv);
-  else
-    LGX_LAUNCH(lgx_post_physics_act_kernel, dim3(blocks + act_wgs), dim3(ENV_THREADS), 0, stream, dp, b, step, draws,
-               extras_snapshot, wa, blocks);
-  return hipGetLastError() == hipSuccess ? 0 : -2;
-}
-
-int lgx_launch_reset_idx(const lgx_env_params* dp, const lgx_buffers& b, int32_t n_envs, int32_t n_term_rows,
-                         const int32_t* ids, int32_t n, int64_t step, int32_t init_done, const float* draws,
-                         float* extras_snapshot, int32_t* hist_age, hipStream_t stream) {
-  (void)n_envs; (void)n_term_rows;
+int lgx_launch_reset_idx(const lgx_env_params* dp, const lgx_buffers& b, const int32_t* ids, int32_t n, int64_t step,
+                         int32_t init_done, const float* draws, float* extras_snapshot, int32_t* hist_age,
+                         hipStream_t stream) {
   if (n <= 0) return 0;
   int blocks = (n + LGX_ENV_BLOCK - 1) / LGX_ENV_BLOCK;
   hipLaunchKernelGGL(lgx_reset_idx_kernel, dim3(blocks), dim3(LGX_ENV_BLOCK), 0, stream, dp, b, ids, n, step,
@@ -859,32 +847,26 @@ lgx_post_physics_act_priv_hist_kernel(const lgx_env_params* __restrict__ P, lgx_
   else actuator_ws_body(wa, blockIdx.x - nblocks, gridDim.x - nblocks);
 }
 
-int lgx_launch_post_physics_hist(const lgx_env_params* dp, const lgx_buffers& b, int32_t n_envs, int64_t step,
-                                 const float* draws, float* extras_snapshot, const lgx_priv_args& pv,
-                                 const lgx_hist_args& hv, hipStream_t stream) {
-  int blocks = (n_envs + LGX_ENV_BLOCK - 1) / LGX_ENV_BLOCK;
-  if (pv.buf)
+int lgx_post_physics_hist_select(const lgx_env_params* dp, const lgx_buffers& b, int32_t n_envs, int64_t step,
+                                 const float* draws, float* extras_snapshot, const lgx_act_launch* act,
+                                 const lgx_priv_args& pv, const lgx_hist_args& hv, hipStream_t stream) {
+  const int blocks = (n_envs + LGX_ENV_BLOCK - 1) / LGX_ENV_BLOCK;
+  if (act) {
+    const int act_wgs = actuator_workgroups(act->rows);
+    WsArgs wa{act->in, act->out, act->rows, act->w, act->scale};
+    if (pv.buf)
+      LGX_LAUNCH(lgx_post_physics_act_priv_hist_kernel, dim3(blocks + act_wgs), dim3(ENV_THREADS), 0, stream, dp, b,
+                 step, draws, extras_snapshot, wa, blocks, pv, hv);
+    else
+      LGX_LAUNCH(lgx_post_physics_act_hist_kernel, dim3(blocks + act_wgs), dim3(ENV_THREADS), 0, stream, dp, b, step,
+                 draws, extras_snapshot, wa, blocks, hv);
+  } else if (pv.buf) {
     LGX_LAUNCH(lgx_post_physics_priv_hist_kernel, dim3(blocks), dim3(ENV_THREADS), 0, stream, dp, b, step, draws,
                extras_snapshot, pv, hv);
-  else
+  } else {
     LGX_LAUNCH(lgx_post_physics_hist_kernel, dim3(blocks), dim3(ENV_THREADS), 0, stream, dp, b, step, draws,
                extras_snapshot, hv);
-  return hipGetLastError() == hipSuccess ? 0 : -2;
-}
-
-int lgx_launch_post_physics_act_hist(const lgx_env_params* dp, const lgx_buffers& b, int32_t n_envs, int64_t step,
-                                     const float* draws, float* extras_snapshot, const float* act_in, float* act_out,
-                                     int64_t act_rows, const float* act_w, const float* act_scale,
-                                     const lgx_priv_args& pv, const lgx_hist_args& hv, hipStream_t stream) {
-  const int blocks = (n_envs + LGX_ENV_BLOCK - 1) / LGX_ENV_BLOCK;
-  const int act_wgs = actuator_workgroups(act_rows);
-  WsArgs wa{act_in, act_out, act_rows, act_w, act_scale};
-  if (pv.buf)
-    LGX_LAUNCH(lgx_post_physics_act_priv_hist_kernel, dim3(blocks + act_wgs), dim3(ENV_THREADS), 0, stream, dp, b,
-               step, draws, extras_snapshot, wa, blocks, pv, hv);
-  else
-    LGX_LAUNCH(lgx_post_physics_act_hist_kernel, dim3(blocks + act_wgs), dim3(ENV_THREADS), 0, stream, dp, b, step,
-               draws, extras_snapshot, wa, blocks, hv);
+  }
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 

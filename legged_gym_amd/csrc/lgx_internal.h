@@ -72,29 +72,29 @@ struct lgx_hist_args {
   int32_t* age;
   int32_t frames, frame_width, width;
 };
-// pv.buf == nullptr and hv.row == nullptr launch the kernels of a sim with neither bound (no other
-// kernel argument or code); otherwise the instantiation with the privileged row, the history or both
-int lgx_launch_post_physics(const lgx_env_params* dp, const lgx_buffers& b, int32_t n_envs, int32_t num_obs,
-                            int32_t n_term_rows, int32_t measure_heights, int64_t step, const float* draws,
-                            float* extras_snapshot, const lgx_priv_args& pv, const lgx_hist_args& hv,
-                            hipStream_t stream);
-// post-physics + the Go1 actuator net (act_rows rows of act_in -> act_out) in one launch
-int lgx_launch_post_physics_act(const lgx_env_params* dp, const lgx_buffers& b, int32_t n_envs, int64_t step,
-                                const float* draws, float* extras_snapshot, const float* act_in, float* act_out,
-                                int64_t act_rows, const float* act_w, const float* act_scale,
-                                const lgx_priv_args& pv, const lgx_hist_args& hv, hipStream_t stream);
-// the same two launches with a history bound (hv.row != nullptr; lgx_envlogic_hist.hip), to which the two above forward
-int lgx_launch_post_physics_hist(const lgx_env_params* dp, const lgx_buffers& b, int32_t n_envs, int64_t step,
-                                 const float* draws, float* extras_snapshot, const lgx_priv_args& pv,
-                                 const lgx_hist_args& hv, hipStream_t stream);
-int lgx_launch_post_physics_act_hist(const lgx_env_params* dp, const lgx_buffers& b, int32_t n_envs, int64_t step,
-                                     const float* draws, float* extras_snapshot, const float* act_in, float* act_out,
-                                     int64_t act_rows, const float* act_w, const float* act_scale,
-                                     const lgx_priv_args& pv, const lgx_hist_args& hv, hipStream_t stream);
+// the Go1 actuator net's share of a post-physics launch: `rows` rows of `in` -> `out` on persistent
+// workgroups behind the post-physics ones (lgx_actuator_mlp's arguments)
+struct lgx_act_launch {
+  const float* in;
+  float* out;
+  int64_t rows;
+  const float* w;
+  const float* scale;
+};
+// The post-physics launch, one kernel out of eight: act == nullptr: no actuator workgroups;
+// pv.buf == nullptr and hv.row == nullptr: the kernels of a sim with neither bound (no other kernel
+// argument or code), otherwise the instantiation with the privileged row, the history or both.
+int lgx_launch_post_physics(const lgx_env_params* dp, const lgx_buffers& b, int32_t n_envs, int64_t step,
+                            const float* draws, float* extras_snapshot, const lgx_act_launch* act,
+                            const lgx_priv_args& pv, const lgx_hist_args& hv, hipStream_t stream);
+// its choice among the four history kernels (hv.row != nullptr), which live in lgx_envlogic_hist.hip
+int lgx_post_physics_hist_select(const lgx_env_params* dp, const lgx_buffers& b, int32_t n_envs, int64_t step,
+                                 const float* draws, float* extras_snapshot, const lgx_act_launch* act,
+                                 const lgx_priv_args& pv, const lgx_hist_args& hv, hipStream_t stream);
 // hist_age: the bound history's ages (zeroed for the listed envs) or nullptr
-int lgx_launch_reset_idx(const lgx_env_params* dp, const lgx_buffers& b, int32_t n_envs, int32_t n_term_rows,
-                         const int32_t* ids, int32_t n, int64_t step, int32_t init_done, const float* draws,
-                         float* extras_snapshot, int32_t* hist_age, hipStream_t stream);
+int lgx_launch_reset_idx(const lgx_env_params* dp, const lgx_buffers& b, const int32_t* ids, int32_t n, int64_t step,
+                         int32_t init_done, const float* draws, float* extras_snapshot, int32_t* hist_age,
+                         hipStream_t stream);
 // the command curriculum of a sim (lgx_bind_command_curriculum, checked there), passed by value to
 // the decide launch; state == nullptr: nothing bound.  changed: the sim's device int32, written by
 // every decide launch (1: the range moved) and read by the patch launch behind it

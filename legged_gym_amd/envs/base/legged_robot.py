@@ -135,11 +135,8 @@ class LgxBackend:
     def sync_aux(self):
         self._check(self.lib.lgx_sync_aux(self.handle, self.stream()), "lgx_sync_aux")
 
-    BUFFER_IDS = ("root_states", "dof_state", "dof_targets", "torques", "contact_forces", "actions",
-                  "last_actions", "last_dof_vel", "last_root_vel", "commands", "base_lin_vel", "base_ang_vel",
-                  "projected_gravity", "feet_air_time", "obs", "rew", "reset", "time_out", "episode_length",
-                  "episode_sums", "measured_heights", "env_origins", "terrain_levels", "terrain_types", "extras")
-    DTYPES = (torch.float32, torch.uint8, torch.int64)
+    BUFFER_IDS = abi.BUFFER_IDS
+    DTYPES = tuple(getattr(torch, name) for name in abi.DTYPES.values())
 
     def buffer(self, name):
         """lgx_sim_buffer: (device pointer, shape, torch dtype) of a state tensor the sim writes

@@ -966,7 +966,7 @@ class FusedPPOUpdate:
             raise RuntimeError(f"LGX_NATIVE_ALLREDUCE=1: torch's RCCL ({path}) is missing; refusing to load another "
                                "RCCL instance into the process")
         path = path.encode()
-        uid = torch.zeros(128, dtype=torch.uint8)
+        uid = torch.zeros(abi.COMM_ID_BYTES, dtype=torch.uint8)
         if dist.get_rank() == 0:
             self.check(self.lib.lgx_comm_unique_id(path, C.cast(uid.data_ptr(), C.POINTER(C.c_uint8))),
                        "comm_unique_id")

@@ -1,7 +1,10 @@
 """ctypes mirror of include/lgx.h (the C-ABI of liblgx.so).
 
-The struct layouts below must match the header field for field; `check_layout(lib)` compares
-them with the library's own `lgx_struct_sizes` so a drift fails loudly at load time.
+Everything Python repeats from the header is stated here once, in three tables: STRUCTS (the
+structures, field for field), SIGS (every prototype) and CONSTANTS (every #define / enum value with
+the Python value that mirrors it).  tests/test_abi_host.py compiles a probe against the header alone
+and compares all three, offsets and argument widths included; `check_layout` is the load-time guard
+against a stale library, from the library's own `lgx_struct_sizes`.
 This module only describes the ABI; loading the product library is `legged_gym_amd.sim.lib`.
 """
 import ctypes as C
@@ -24,11 +27,18 @@ REWARD_IDS = {
     "feet_contact_forces": 19, "hip_motion": 20, "no_fly": 21,
 }
 CTRL = {"POS_DRIVE": 0, "P": 1, "V": 2, "T": 3, "SEA": 4}
+# enum lgx_buffer_id in order: the state tensors lgx_sim_buffer reports; enum lgx_dtype in order,
+# each with the name of its torch dtype
+BUFFER_IDS = ("root_states", "dof_state", "dof_targets", "torques", "contact_forces", "actions",
+              "last_actions", "last_dof_vel", "last_root_vel", "commands", "base_lin_vel", "base_ang_vel",
+              "projected_gravity", "feet_air_time", "obs", "rew", "reset", "time_out", "episode_length",
+              "episode_sums", "measured_heights", "env_origins", "terrain_levels", "terrain_types", "extras")
+DTYPES = {"F32": "float32", "U8": "uint8", "I64": "int64"}
 
 DRAW_CMD, DRAW_PUSH, DRAW_RESET_DOF, DRAW_RESET_XY = 0, 3, 5, 17
 DRAW_RESET_VEL, DRAW_RESET_CMD, DRAW_CURRIC, DRAW_NOISE = 19, 25, 28, 32
 
-f32, i32, i64, u64 = C.c_float, C.c_int32, C.c_int64, C.c_uint64
+f32, i32, i64, u64, vp = C.c_float, C.c_int32, C.c_int64, C.c_uint64, C.c_void_p
 PF, PU8, PI64, PI16, PI32 = C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_int64), C.POINTER(C.c_int16), C.POINTER(C.c_int32)
 
 
@@ -191,151 +201,168 @@ OBS_NORM_MAX_JOBS = 2     # LGX_OBS_NORM_MAX_JOBS
 PPO_MAX_ACTIONS = 16
 MAX_REDUCE_JOBS = 16
 EPISODE_RING_MAX = 4096   # LGX_EPISODE_RING_MAX: largest ring of lgx_episode_stats_step
+COMM_ID_BYTES = 128       # LGX_COMM_ID_BYTES: the unique id of lgx_comm_unique_id / lgx_comm_create
 GEMM_PLAIN, GEMM_BIAS_ELU, GEMM_DELU_COLSUM, GEMM_DELU = 0, 1, 2, 3
 GEMM_ALGO_DEFAULT, GEMM_ALGO_F32, GEMM_ALGO_SPLIT_BF16 = 0, 1, 2
 GEMM_TILE_M, GEMM_TILE_N, GEMM_K_STEP = 128, 128, 32   # K step: layer-1 rows padded to 1024 B (aligned 128-B lines)
 
 
+# Every prototype of lgx.h as (restype, argtypes), keyed by the name after the library's prefix: the
+# entry points the CPU oracle shares in form, then the product library's own.  `declare` attaches
+# them, EXPORTED is their names, and tests/test_abi_host.py checks each against the header.
+SIGS_COMMON = {
+    "last_error": (C.c_char_p, []),
+    "version": (C.c_int, []),
+    "struct_sizes": (None, [C.POINTER(C.c_int64)]),
+    "scratch_floats": (C.c_int64, [i32, i32]),
+    "sim_create": (C.c_int, [C.POINTER(LgxModel), C.POINTER(LgxEnvParams), C.POINTER(LgxBuffers), C.c_int,
+                             C.POINTER(vp)]),
+    "sim_destroy": (C.c_int, [vp]),
+    "step": (C.c_int, [vp, i64, vp]),
+    "simulate": (C.c_int, [vp, i32, vp]),
+    "post_physics": (C.c_int, [vp, i64, vp]),
+    "post_physics_fused": (C.c_int, [vp, i64, vp]),
+    "reset_idx": (C.c_int, [vp, vp, i32, i64, i32, vp]),
+    "set_draws": (C.c_int, [vp, vp]),
+    "rebind_obs": (C.c_int, [vp, vp]),
+    "actuator_mlp": (C.c_int, [vp, vp, i64, vp, vp, vp]),
+    "actuator_lstm": (C.c_int, [vp, vp, vp, vp, i64, vp, vp]),
+    "mlp_forward": (C.c_int, [vp, vp, i64, i32, C.POINTER(i32), C.POINTER(vp), C.POINTER(vp), i32, vp]),
+    "gae": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, C.c_float, C.c_float, vp]),
+    "gae_norm_scratch": (i64, [i32]),
+    "gae_norm": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, C.c_float, C.c_float, vp, vp]),
+    "gae_parts": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, C.c_float, C.c_float, vp, vp]),
+    "adv_norm": (C.c_int, [vp, i64, vp, i32, vp]),
+    "profile_enable": (C.c_int, [vp, i32]),
+    "mlp_forward_batch": (C.c_int, [C.POINTER(LgxMlpDesc), i32, vp]),
+    "profile_collect": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
+}
+SIGS_PRODUCT = {  # PPO update entry points and the later features: product library only
+    "physics_lane_split": (i32, [i32]),
+    "trimesh_build": (C.c_int, [vp, i32, i32, C.c_double, C.c_double, C.c_double, vp, vp, vp, vp]),
+    "step_from": (C.c_int, [vp, vp, i64, vp]),
+    "drive_inputs": (C.c_int, [vp, vp, vp]),
+    "ground_contact": (C.c_int, [vp, vp, i32, vp, vp]),
+    "sync_aux": (C.c_int, [vp, vp]),
+    "rebind_extras": (C.c_int, [vp, vp]),
+    "bind_privileged_obs": (C.c_int, [vp, vp, C.POINTER(LgxPrivObsDesc)]),
+    "rebind_privileged_obs": (C.c_int, [vp, vp]),
+    "bind_obs_history": (C.c_int, [vp, vp, vp, C.POINTER(LgxObsHistoryDesc)]),
+    "rebind_obs_history": (C.c_int, [vp, vp, vp]),
+    "bind_actuator_rand": (C.c_int, [vp, C.POINTER(LgxActuatorRandDesc)]),
+    "bind_command_curriculum": (C.c_int, [vp, C.POINTER(LgxCmdCurriculumDesc)]),
+    "is_curriculum_step": (i32, [i64, C.c_float]),
+    "set_command_range": (C.c_int, [vp, i32, C.c_float, C.c_float, vp]),
+    "sim_buffer": (C.c_int, [vp, i32, C.POINTER(vp), C.POINTER(i64), C.POINTER(i32), C.POINTER(i32)]),
+    "ppo_gather_rows": (C.c_int, [vp, vp, vp, i64, i32, vp]),
+    "ppo_act": (C.c_int, [C.POINTER(LgxPpoActArgs), vp]),
+    "ppo_store": (C.c_int, [C.POINTER(LgxPpoStoreArgs), vp]),
+    "ppo_act_store": (C.c_int, [C.POINTER(LgxPpoActArgs), C.POINTER(LgxPpoStoreArgs), vp]),
+    "bias_act": (C.c_int, [vp, vp, i64, i32, i32, i32, vp]),
+    "ppo_loss_partials_floats": (i64, [i64, i32]),
+    "ppo_loss": (C.c_int, [C.POINTER(LgxPpoLossArgs), vp]),
+    "ppo_adapt_lr": (C.c_int, [vp, C.c_float, vp, C.c_double, vp]),
+    "head_bwd_partials_floats": (i64, [i64, i32, i32]),
+    "head_bwd": (C.c_int, [vp, vp, vp, vp, vp, i64, i32, i32, vp, vp]),
+    "head_bwd_finalize": (C.c_int, [C.POINTER(LgxPpoLossArgs), vp, vp, vp, vp, vp, i64, i32, i32, vp, vp]),
+    "colsum_partials_floats": (i64, [i64, i32, i32]),
+    "elu_bwd_colsum": (C.c_int, [vp, vp, i64, i32, i32, vp, vp]),
+    "reduce_slices": (C.c_int, [C.POINTER(LgxReduceJob), i32, vp]),
+    "reduce_slices_finalize": (C.c_int, [C.POINTER(LgxReduceJob), i32, C.POINTER(LgxPpoLossArgs), vp]),
+    "reduce_slices_blocks": (i64, [C.POINTER(LgxReduceJob), i32, i32]),
+    "reduce_slices_sq": (C.c_int, [C.POINTER(LgxReduceJob), i32, C.POINTER(LgxPpoLossArgs), vp, vp, vp]),
+    "ppo_loss_bwd_layout": (C.c_int, [i64, i32, i32, C.POINTER(i64)]),
+    "ppo_loss_bwd": (C.c_int, [C.POINTER(LgxPpoLossArgs), vp, vp]),
+    "mlp_x3_weight_elems": (i64, [i32, i32]),
+    "mlp_x3_split": (C.c_int, [vp, i32, i32, vp, vp]),
+    "mlp_x3_split_layers": (C.c_int, [C.POINTER(vp), C.POINTER(i32), i32, C.POINTER(vp), vp]),
+    "mlp_x3_lds_bytes": (i64, [C.POINTER(LgxMlpX3Desc), i32]),
+    "mlp_x3_forward": (C.c_int, [C.POINTER(LgxMlpX3Desc), i32, vp]),
+    "mlp_x3_forward_act": (C.c_int, [C.POINTER(LgxMlpX3Desc), i32, C.POINTER(LgxPpoActArgs),
+                                     C.POINTER(LgxPpoStoreArgs), vp]),
+    "gemm_partials_floats": (i64, [i64, i32, i32]),
+    "gemm_nt": (C.c_int, [C.POINTER(LgxGemmArgs), vp]),
+    "gemm_tn": (C.c_int, [C.POINTER(LgxGemmTnArgs), vp]),
+    "copy2d": (C.c_int, [C.POINTER(LgxCopy2dJob), i32, vp]),
+    "split_bf16_elems": (i64, [i32, i32]),
+    "split_bf16": (C.c_int, [C.POINTER(LgxCopy2dJob), i32, vp]),
+    "ppo_gather_rows_padded": (C.c_int, [vp, vp, vp, i64, i32, i32, vp]),
+    "ppo_gather_rows_padded_dup": (C.c_int, [vp, vp, vp, i64, i32, i32, i64, vp]),
+    "adam_clip": (C.c_int, [vp, vp, vp, vp, i64, vp, i32, C.c_float, C.c_float, vp, vp, C.c_float,
+                            C.c_float, C.c_float, vp]),
+    "adam_clip_mirror": (C.c_int, [vp, vp, vp, vp, i64, vp, i32, C.c_float, C.c_float, vp, vp, C.c_float,
+                                   C.c_float, C.c_float, C.POINTER(LgxCopy2dJob), i32, vp]),
+    "adam_clip_mirror_sq": (C.c_int, [vp, vp, vp, vp, i64, vp, i32, C.c_float, vp, vp, C.c_float,
+                                      C.c_float, C.c_float, C.POINTER(LgxCopy2dJob), i32, vp]),
+    "event_create": (C.c_int, [C.POINTER(vp)]),
+    "event_destroy": (C.c_int, [vp]),
+    "event_record": (C.c_int, [vp, vp]),
+    "stream_wait_event": (C.c_int, [vp, vp]),
+    "launch_bind_event": (C.c_int, [vp]),
+    "launch_bind_pending": (C.c_int, []),
+    "comm_unique_id": (C.c_int, [C.c_char_p, C.POINTER(C.c_uint8)]),
+    "comm_create": (C.c_int, [C.c_char_p, C.POINTER(C.c_uint8), i32, i32, i32, C.POINTER(vp)]),
+    "comm_destroy": (C.c_int, [vp]),
+    "allreduce_grads": (C.c_int, [vp, vp, C.c_size_t, i32, vp]),
+    "episode_stats_step": (C.c_int, [vp, vp, i64, vp, vp, vp, vp, i32, vp, vp]),
+    "obs_norm_rows_per_part": (i32, []),
+    "obs_norm_part_doubles": (i64, [i64, i32]),
+    "obs_norm_partials": (C.c_int, [C.POINTER(LgxObsNormJob), i32, vp]),
+    "obs_norm_apply": (C.c_int, [C.POINTER(LgxObsNormJob), i32, vp]),
+    "ppo_symmetry_augment": (C.c_int, [C.POINTER(LgxSymmetryArgs), vp]),
+    "ppo_symmetry_check_table": (C.c_int, [vp, vp, i32]),
+}
+SIGS = {**SIGS_COMMON, **SIGS_PRODUCT}
+EXPORTED = [f"lgx_{name}" for name in SIGS]
+
+
 def declare(lib, prefix="lgx"):
     """Attach argtypes/restypes of the product C-ABI to a loaded CDLL."""
-    vp = C.c_void_p
-    sigs = {
-        "last_error": (C.c_char_p, []),
-        "version": (C.c_int, []),
-        "struct_sizes": (None, [C.POINTER(C.c_int64)]),
-        "scratch_floats": (C.c_int64, [i32, i32]),
-        "sim_create": (C.c_int, [C.POINTER(LgxModel), C.POINTER(LgxEnvParams), C.POINTER(LgxBuffers), C.c_int,
-                                 C.POINTER(vp)]),
-        "sim_destroy": (C.c_int, [vp]),
-        "step": (C.c_int, [vp, i64, vp]),
-        "simulate": (C.c_int, [vp, i32, vp]),
-        "post_physics": (C.c_int, [vp, i64, vp]),
-        "post_physics_fused": (C.c_int, [vp, i64, vp]),
-        "reset_idx": (C.c_int, [vp, vp, i32, i64, i32, vp]),
-        "set_draws": (C.c_int, [vp, vp]),
-        "rebind_obs": (C.c_int, [vp, vp]),
-        "actuator_mlp": (C.c_int, [vp, vp, i64, vp, vp, vp]),
-        "actuator_lstm": (C.c_int, [vp, vp, vp, vp, i64, vp, vp]),
-        "mlp_forward": (C.c_int, [vp, vp, i64, i32, C.POINTER(i32), C.POINTER(vp), C.POINTER(vp), i32, vp]),
-        "gae": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, C.c_float, C.c_float, vp]),
-        "gae_norm_scratch": (i64, [i32]),
-        "gae_norm": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, C.c_float, C.c_float, vp, vp]),
-        "gae_parts": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, C.c_float, C.c_float, vp, vp]),
-        "adv_norm": (C.c_int, [vp, i64, vp, i32, vp]),
-        "profile_enable": (C.c_int, [vp, i32]),
-        "mlp_forward_batch": (C.c_int, [C.POINTER(LgxMlpDesc), i32, vp]),
-        "profile_collect": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
-    }
-    if prefix == "lgx":  # PPO update entry points: product library only
-        sigs.update({
-            "physics_lane_split": (i32, [i32]),
-            "trimesh_build": (C.c_int, [vp, i32, i32, C.c_double, C.c_double, C.c_double, vp, vp, vp, vp]),
-            "step_from": (C.c_int, [vp, vp, i64, vp]),
-            "drive_inputs": (C.c_int, [vp, vp, vp]),
-            "ground_contact": (C.c_int, [vp, vp, i32, vp, vp]),
-            "sync_aux": (C.c_int, [vp, vp]),
-            "rebind_extras": (C.c_int, [vp, vp]),
-            "bind_privileged_obs": (C.c_int, [vp, vp, C.POINTER(LgxPrivObsDesc)]),
-            "rebind_privileged_obs": (C.c_int, [vp, vp]),
-            "bind_obs_history": (C.c_int, [vp, vp, vp, C.POINTER(LgxObsHistoryDesc)]),
-            "rebind_obs_history": (C.c_int, [vp, vp, vp]),
-            "bind_actuator_rand": (C.c_int, [vp, C.POINTER(LgxActuatorRandDesc)]),
-            "bind_command_curriculum": (C.c_int, [vp, C.POINTER(LgxCmdCurriculumDesc)]),
-            "cmd_curriculum_desc_layout": (None, [C.POINTER(C.c_int64)]),
-            "is_curriculum_step": (i32, [i64, C.c_float]),
-            "set_command_range": (C.c_int, [vp, i32, C.c_float, C.c_float, vp]),
-            "sim_buffer": (C.c_int, [vp, i32, C.POINTER(vp), C.POINTER(i64), C.POINTER(i32), C.POINTER(i32)]),
-            "ppo_gather_rows": (C.c_int, [vp, vp, vp, i64, i32, vp]),
-            "ppo_act": (C.c_int, [C.POINTER(LgxPpoActArgs), vp]),
-            "ppo_store": (C.c_int, [C.POINTER(LgxPpoStoreArgs), vp]),
-            "ppo_act_store": (C.c_int, [C.POINTER(LgxPpoActArgs), C.POINTER(LgxPpoStoreArgs), vp]),
-            "bias_act": (C.c_int, [vp, vp, i64, i32, i32, i32, vp]),
-            "ppo_loss_partials_floats": (i64, [i64, i32]),
-            "ppo_loss": (C.c_int, [C.POINTER(LgxPpoLossArgs), vp]),
-            "ppo_adapt_lr": (C.c_int, [vp, C.c_float, vp, C.c_double, vp]),
-            "head_bwd_partials_floats": (i64, [i64, i32, i32]),
-            "head_bwd": (C.c_int, [vp, vp, vp, vp, vp, i64, i32, i32, vp, vp]),
-            "head_bwd_finalize": (C.c_int, [C.POINTER(LgxPpoLossArgs), vp, vp, vp, vp, vp, i64, i32, i32, vp, vp]),
-            "colsum_partials_floats": (i64, [i64, i32, i32]),
-            "elu_bwd_colsum": (C.c_int, [vp, vp, i64, i32, i32, vp, vp]),
-            "reduce_slices": (C.c_int, [C.POINTER(LgxReduceJob), i32, vp]),
-            "reduce_slices_finalize": (C.c_int, [C.POINTER(LgxReduceJob), i32, C.POINTER(LgxPpoLossArgs), vp]),
-            "reduce_slices_blocks": (i64, [C.POINTER(LgxReduceJob), i32, i32]),
-            "reduce_slices_sq": (C.c_int, [C.POINTER(LgxReduceJob), i32, C.POINTER(LgxPpoLossArgs), vp, vp, vp]),
-            "ppo_loss_bwd_layout": (C.c_int, [i64, i32, i32, C.POINTER(i64)]),
-            "ppo_loss_bwd": (C.c_int, [C.POINTER(LgxPpoLossArgs), vp, vp]),
-            "mlp_x3_weight_elems": (i64, [i32, i32]),
-            "mlp_x3_split": (C.c_int, [vp, i32, i32, vp, vp]),
-            "mlp_x3_split_layers": (C.c_int, [C.POINTER(vp), C.POINTER(i32), i32, C.POINTER(vp), vp]),
-            "mlp_x3_lds_bytes": (i64, [C.POINTER(LgxMlpX3Desc), i32]),
-            "mlp_x3_forward": (C.c_int, [C.POINTER(LgxMlpX3Desc), i32, vp]),
-            "mlp_x3_forward_act": (C.c_int, [C.POINTER(LgxMlpX3Desc), i32, C.POINTER(LgxPpoActArgs),
-                                             C.POINTER(LgxPpoStoreArgs), vp]),
-            "gemm_partials_floats": (i64, [i64, i32, i32]),
-            "gemm_nt": (C.c_int, [C.POINTER(LgxGemmArgs), vp]),
-            "gemm_tn": (C.c_int, [C.POINTER(LgxGemmTnArgs), vp]),
-            "copy2d": (C.c_int, [C.POINTER(LgxCopy2dJob), i32, vp]),
-            "split_bf16_elems": (i64, [i32, i32]),
-            "split_bf16": (C.c_int, [C.POINTER(LgxCopy2dJob), i32, vp]),
-            "ppo_gather_rows_padded": (C.c_int, [vp, vp, vp, i64, i32, i32, vp]),
-            "ppo_gather_rows_padded_dup": (C.c_int, [vp, vp, vp, i64, i32, i32, i64, vp]),
-            "adam_clip": (C.c_int, [vp, vp, vp, vp, i64, vp, i32, C.c_float, C.c_float, vp, vp, C.c_float,
-                                    C.c_float, C.c_float, vp]),
-            "adam_clip_mirror": (C.c_int, [vp, vp, vp, vp, i64, vp, i32, C.c_float, C.c_float, vp, vp, C.c_float,
-                                           C.c_float, C.c_float, C.POINTER(LgxCopy2dJob), i32, vp]),
-            "adam_clip_mirror_sq": (C.c_int, [vp, vp, vp, vp, i64, vp, i32, C.c_float, vp, vp, C.c_float,
-                                              C.c_float, C.c_float, C.POINTER(LgxCopy2dJob), i32, vp]),
-            "event_create": (C.c_int, [C.POINTER(vp)]),
-            "event_destroy": (C.c_int, [vp]),
-            "event_record": (C.c_int, [vp, vp]),
-            "stream_wait_event": (C.c_int, [vp, vp]),
-            "launch_bind_event": (C.c_int, [vp]),
-            "launch_bind_pending": (C.c_int, []),
-            "comm_unique_id": (C.c_int, [C.c_char_p, C.POINTER(C.c_uint8)]),
-            "comm_create": (C.c_int, [C.c_char_p, C.POINTER(C.c_uint8), i32, i32, i32, C.POINTER(vp)]),
-            "comm_destroy": (C.c_int, [vp]),
-            "allreduce_grads": (C.c_int, [vp, vp, C.c_size_t, i32, vp]),
-            "episode_stats_step": (C.c_int, [vp, vp, i64, vp, vp, vp, vp, i32, vp, vp]),
-            "obs_norm_rows_per_part": (i32, []),
-            "obs_norm_part_doubles": (i64, [i64, i32]),
-            "obs_norm_partials": (C.c_int, [C.POINTER(LgxObsNormJob), i32, vp]),
-            "obs_norm_apply": (C.c_int, [C.POINTER(LgxObsNormJob), i32, vp]),
-            "ppo_symmetry_augment": (C.c_int, [C.POINTER(LgxSymmetryArgs), vp]),
-            "ppo_symmetry_check_table": (C.c_int, [vp, vp, i32]),
-        })
-    for name, (res, args) in sigs.items():
+    for name, (res, args) in (SIGS if prefix == "lgx" else SIGS_COMMON).items():
         fn = getattr(lib, f"{prefix}_{name}")
         fn.restype = res
         fn.argtypes = args
     return lib
 
 
-EXPORTED = ["lgx_last_error", "lgx_version", "lgx_physics_lane_split", "lgx_trimesh_build", "lgx_struct_sizes", "lgx_scratch_floats", "lgx_sim_create",
-            "lgx_sim_destroy", "lgx_step", "lgx_simulate", "lgx_post_physics", "lgx_post_physics_fused", "lgx_reset_idx", "lgx_set_draws", "lgx_rebind_obs", "lgx_rebind_extras", "lgx_bind_privileged_obs", "lgx_rebind_privileged_obs", "lgx_bind_obs_history", "lgx_rebind_obs_history", "lgx_bind_actuator_rand", "lgx_bind_command_curriculum", "lgx_cmd_curriculum_desc_layout", "lgx_is_curriculum_step", "lgx_set_command_range", "lgx_sim_buffer", "lgx_step_from", "lgx_drive_inputs", "lgx_ground_contact", "lgx_sync_aux",
-            "lgx_actuator_mlp", "lgx_actuator_lstm", "lgx_mlp_forward", "lgx_gae", "lgx_gae_norm_scratch", "lgx_gae_norm", "lgx_gae_parts", "lgx_adv_norm",
-            "lgx_profile_enable", "lgx_profile_collect", "lgx_mlp_forward_batch",
-            "lgx_ppo_gather_rows", "lgx_bias_act", "lgx_ppo_loss_partials_floats", "lgx_ppo_loss", "lgx_ppo_adapt_lr",
-            "lgx_head_bwd_partials_floats", "lgx_head_bwd", "lgx_head_bwd_finalize", "lgx_colsum_partials_floats", "lgx_elu_bwd_colsum",
-            "lgx_reduce_slices", "lgx_reduce_slices_finalize", "lgx_ppo_loss_bwd_layout", "lgx_ppo_loss_bwd", "lgx_adam_clip", "lgx_adam_clip_mirror", "lgx_adam_clip_mirror_sq", "lgx_reduce_slices_blocks", "lgx_reduce_slices_sq", "lgx_ppo_act", "lgx_ppo_store", "lgx_ppo_act_store",
-            "lgx_gemm_partials_floats", "lgx_gemm_nt", "lgx_copy2d", "lgx_ppo_gather_rows_padded",
-            "lgx_ppo_gather_rows_padded_dup", "lgx_split_bf16_elems", "lgx_split_bf16", "lgx_gemm_tn",
-            "lgx_mlp_x3_weight_elems", "lgx_mlp_x3_split", "lgx_mlp_x3_split_layers", "lgx_mlp_x3_lds_bytes", "lgx_mlp_x3_forward", "lgx_mlp_x3_forward_act",
-            "lgx_event_create", "lgx_event_destroy", "lgx_event_record", "lgx_stream_wait_event",
-            "lgx_launch_bind_event", "lgx_launch_bind_pending",
-            "lgx_comm_unique_id", "lgx_comm_create", "lgx_comm_destroy", "lgx_allreduce_grads",
-            "lgx_episode_stats_step",
-            "lgx_obs_norm_rows_per_part", "lgx_obs_norm_part_doubles", "lgx_obs_norm_partials", "lgx_obs_norm_apply",
-            "lgx_ppo_symmetry_augment", "lgx_ppo_symmetry_check_table"]
+# The ABI structures with their C names; the first 12 in lgx_struct_sizes order.
+STRUCTS = [
+    (LgxModel, "lgx_model"), (LgxEnvParams, "lgx_env_params"), (LgxBuffers, "lgx_buffers"),
+    (LgxMlpDesc, "lgx_mlp_desc"), (LgxPpoLossArgs, "lgx_ppo_loss_args"), (LgxReduceJob, "lgx_reduce_job"),
+    (LgxPpoActArgs, "lgx_ppo_act_args"), (LgxPpoStoreArgs, "lgx_ppo_store_args"), (LgxGemmArgs, "lgx_gemm_args"),
+    (LgxCopy2dJob, "lgx_copy2d_job"), (LgxGemmTnArgs, "lgx_gemm_tn_args"), (LgxMlpX3Desc, "lgx_mlp_x3_desc"),
+    (LgxPrivObsDesc, "lgx_priv_obs_desc"), (LgxObsHistoryDesc, "lgx_obs_history_desc"),
+    (LgxActuatorRandDesc, "lgx_actuator_rand_desc"), (LgxCmdCurriculumDesc, "lgx_cmd_curriculum_desc"),
+    (LgxObsNormJob, "lgx_obs_norm_job"), (LgxSymmetryArgs, "lgx_symmetry_args"),
+]
+
+# C identifier -> the Python value that mirrors it, for every constant of lgx.h repeated above
+CONSTANTS = {
+    "LGX_NUM_DOF": NUM_DOF, "LGX_NUM_DYN": NUM_DYN, "LGX_MAX_BODIES": MAX_BODIES, "LGX_MAX_POINTS": MAX_POINTS,
+    "LGX_MAX_OBS": MAX_OBS, "LGX_MAX_HEIGHT_POINTS": MAX_HEIGHT_POINTS, "LGX_MAX_TERMS": MAX_TERMS,
+    **{f"LGX_R_{k.upper()}": v for k, v in REWARD_IDS.items()}, "LGX_R_COUNT": len(REWARD_IDS),
+    **{f"LGX_CTRL_{k}": v for k, v in CTRL.items()},
+    "LGX_DRAW_CMD": DRAW_CMD, "LGX_DRAW_PUSH": DRAW_PUSH, "LGX_DRAW_RESET_DOF": DRAW_RESET_DOF,
+    "LGX_DRAW_RESET_XY": DRAW_RESET_XY, "LGX_DRAW_RESET_VEL": DRAW_RESET_VEL, "LGX_DRAW_RESET_CMD": DRAW_RESET_CMD,
+    "LGX_DRAW_CURRIC": DRAW_CURRIC, "LGX_DRAW_NOISE": DRAW_NOISE,
+    **{f"LGX_PRIV_{k.upper()}": v for k, v in PRIV_TERM_IDS.items()}, "LGX_PRIV_COUNT": len(PRIV_TERM_IDS),
+    "LGX_MAX_PRIV_OBS": MAX_PRIV_OBS, "LGX_PRIV_MAX_TERMS": PRIV_MAX_TERMS,
+    "LGX_OBS_NORM_ROWS": OBS_NORM_ROWS, "LGX_OBS_NORM_MAX_JOBS": OBS_NORM_MAX_JOBS,
+    "LGX_PPO_MAX_ACTIONS": PPO_MAX_ACTIONS, "LGX_MAX_REDUCE_JOBS": MAX_REDUCE_JOBS,
+    "LGX_EPISODE_RING_MAX": EPISODE_RING_MAX, "LGX_COMM_ID_BYTES": COMM_ID_BYTES,
+    "LGX_GEMM_PLAIN": GEMM_PLAIN, "LGX_GEMM_BIAS_ELU": GEMM_BIAS_ELU, "LGX_GEMM_DELU_COLSUM": GEMM_DELU_COLSUM,
+    "LGX_GEMM_DELU": GEMM_DELU, "LGX_GEMM_ALGO_DEFAULT": GEMM_ALGO_DEFAULT, "LGX_GEMM_ALGO_F32": GEMM_ALGO_F32,
+    "LGX_GEMM_ALGO_SPLIT_BF16": GEMM_ALGO_SPLIT_BF16,
+    **{f"LGX_BUF_{k.upper()}": v for v, k in enumerate(BUFFER_IDS)}, "LGX_BUF_COUNT": len(BUFFER_IDS),
+    **{f"LGX_{k}": v for v, k in enumerate(DTYPES)},
+}
 
 
 def check_layout(sizes_fn, n=12):
-    """Compare the library's sizeof() of every ABI struct with these mirrors (the oracle
+    """Compare the library's sizeof() of the first n ABI structs with these mirrors (the oracle
     reports the first 3)."""
     out = (C.c_int64 * 16)()
     sizes_fn(out)
-    mine = (C.sizeof(LgxModel), C.sizeof(LgxEnvParams), C.sizeof(LgxBuffers), C.sizeof(LgxMlpDesc),
-            C.sizeof(LgxPpoLossArgs), C.sizeof(LgxReduceJob), C.sizeof(LgxPpoActArgs),
-            C.sizeof(LgxPpoStoreArgs), C.sizeof(LgxGemmArgs), C.sizeof(LgxCopy2dJob), C.sizeof(LgxGemmTnArgs),
-            C.sizeof(LgxMlpX3Desc))[:n]
+    mine = tuple(C.sizeof(cls) for cls, _ in STRUCTS[:n])
     if tuple(out)[:n] != mine:
         raise RuntimeError(f"lgx ABI layout mismatch: library {tuple(out)[:n]} vs bindings {mine}")

