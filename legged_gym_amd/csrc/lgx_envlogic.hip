@@ -14,6 +14,7 @@
 
 #include "lgx_device.h"
 #include "lgx_internal.h"
+#include "lgx_launch.h"
 #include "lgx_actuator_ws.h"
 
 #define ENV_THREADS (16 * LGX_ENV_BLOCK)
@@ -697,9 +698,7 @@ LGX_DEV void post_physics_body(const lgx_env_params* __restrict__ P, const lgx_b
 // one persistent actuator workgroup per CU next to the post-physics workgroups
 int actuator_workgroups(int64_t act_rows) {
   const int64_t tiles = (act_rows + WS_BM - 1) / WS_BM;
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  return (int)std::max<int64_t>(1, std::min<int64_t>(tiles, cus));
+  return (int)std::max<int64_t>(1, std::min<int64_t>(tiles, lgx_cu_count()));
 }
 
 }  // namespace

@@ -302,14 +302,10 @@ extern "C" int lgx_gemm_nt(const lgx_gemm_args* args, void* stream) {
   constexpr int prio = 1;   // s_setprio around the MFMA stages
   GemmArgs g{a.M, a.N, a.K, a.batch, a.epi, a.A, a.lda, a.sa, a.B, a.ldb, a.sb, a.C, a.ldc, a.sc, a.bias, a.Y,
              a.partials, prio, nullptr};
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  const int64_t per_xcd = (tiles + 7) / 8;
+  const int cus = lgx_cu_count();
   if (algo == LGX_GEMM_ALGO_SPLIT_BF16) return lgx_gemm_nt_split(a, cus, stream);
   if (a.epi == LGX_GEMM_DELU) return lgx_fail(LGX_EINVAL, "lgx_gemm_nt: LGX_GEMM_DELU needs the split-bf16 algo");
-  // persistent: 2 workgroups per CU (LDS-bound), a multiple of 8 (XCD tile ranges)
-  const int64_t wgs = 8 * std::min<int64_t>(per_xcd, std::max(1, 2 * cus / 8));
-  const dim3 grid((unsigned)wgs);
+  const dim3 grid((unsigned)lgx_xcd_grid(tiles, cus, 2));   // LDS-bound: 2 workgroups per CU
   const dim3 block(512);   // 8 waves per 128 x 128 tile
   if (a.epi == LGX_GEMM_BIAS_ELU) LGX_LAUNCH((gemm_nt_kernel<8, LGX_GEMM_BIAS_ELU>), grid, block, 0, LGX_STREAM(stream), g);
   else if (a.epi == LGX_GEMM_DELU_COLSUM)

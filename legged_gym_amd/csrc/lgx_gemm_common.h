@@ -13,10 +13,13 @@
 #include <type_traits>
 
 #include "lgx_internal.h"
+#include "lgx_launch.h"
+#include "lgx_split_bf16.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using f32x16 = lgx_f32x16;
+using bf16x8 = lgx_bf16x8;
 
 constexpr int BM = 128;     // rows per workgroup tile
 constexpr int BN = 128;     // columns per workgroup tile

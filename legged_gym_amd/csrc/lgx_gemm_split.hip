@@ -1,22 +1,8 @@
 // Split-bf16 evaluation of the PPO-update GEMM products on the bf16 MFMA
 // (v_mfma_f32_32x32x16_bf16, 16x the f32 MFMA rate; gfx950 has no xf32/TF32 path).
 //
-// Every f32 operand is split, round-to-nearest, into three bf16 limbs
-//   x = x0 + x1 + x2 + e,   x0 = bf16(x), x1 = bf16(x - x0), x2 = bf16(x - x0 - x1),
-//   |x1| <= 2^-8 |x0|, |x2| <= 2^-8 |x1|, e = 0 for a normal f32   (both subtractions are exact in f32),
-// and a*b is evaluated as the six limb products of order <= 2,
-//   a0 b0 + (a0 b1 + a1 b0) + (a0 b2 + a1 b1 + a2 b0),
-// each product of two bf16 limbs exact in the f32 accumulator.  The dropped terms (a1 b2, a2 b1,
-// a2 b2) are <= 2.04 * 2^-24 |a b| (far less on average since the limb ratios are spread over the
-// half-ulp range) and the accumulator's roundings of one product <= 5 * 2^-24 |a b|: a single
-// product is within 2^-21 |a b| (tests/split_products_ref.py derives it; measured <= 2.7 * 2^-24
-// on every split-bf16 kernel).  Each 16-k MFMA rounds the accumulator once per limb product (6
-// roundings per 16 k against 16 for the fmaf chain): the result is f32-accurate
-// (tests/test_gpu_split_products.py: every single product within 2^-21, and max / mean error of
-// dense sums vs float64 within 1.25x of the exact-f32 MFMA's on the same operands, on this
-// kernel, the pipelined one, lgx_gemm_tn's and the rollout MLP's).
-// 6 MFMAs at 1/16 the cost of the f32 MFMA's 8 per 16 k: a 2.67x higher arithmetic roof
-// (417 TF/s of f32 products against 157 TF/s).
+// The arithmetic (three RNE bf16 limbs per f32 operand, six limb products, small ones first) and
+// its error bound: lgx_split_bf16.h.
 //
 // Same argument block, tile order (persistent workgroups, XCD-contiguous tile ranges) and fused
 // epilogues as gemm_nt_kernel (lgx_gemm_common.h).  Differences:
@@ -43,28 +29,20 @@
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float fx2 __attribute__((ext_vector_type(2)));
-
+static_assert(BN == LGX_X3_BN && BK == LGX_X3_BK, "a tile column block x K stage is one pre-split block");
 constexpr int NWX = 4;                           // waves per workgroup (2 x 2 waves of 64 x 64)
 constexpr int X3_ROW = 3 * BK * 2 + 16;          // bytes per LDS row (3 limbs of 32 bf16 + pad)
 constexpr int X3_TILE = BM * X3_ROW;             // one operand tile: 26,624 B
 constexpr int X3_LDS = 2 * X3_TILE;              // one stage (A, B): 53,248 B -> 2 workgroups per CU
-constexpr int LIMB_ROW = 3 * BK;                 // bf16 per (row, 32-k block) of a pre-split operand
-constexpr int BCH = BN * LIMB_ROW * 2 / 16 / (64 * NWX);   // 16-byte B chunks per thread per stage (3)
+constexpr int BCH = LGX_X3_BLOCK * 2 / 16 / (64 * NWX);   // 16-byte B chunks per thread per stage (3)
 #ifndef X3_INTERLEAVE
 #define X3_INTERLEAVE 1
 #endif
 
-__device__ __forceinline__ void split2(float x0, float x1, uint32_t& l0, uint32_t& l1, uint32_t& l2) {
-  lgx_split2(x0, x1, l0, l1, l2);   // (lgx_internal.h)
-}
-
 __device__ __forceinline__ void store_split4(char* row, int c, const float4& v) {
   uint32_t a0, a1, a2, b0, b1, b2;
-  split2(v.x, v.y, a0, a1, a2);
-  split2(v.z, v.w, b0, b1, b2);
+  lgx_split2(v.x, v.y, a0, a1, a2);
+  lgx_split2(v.z, v.w, b0, b1, b2);
   *reinterpret_cast<uint2*>(row + 2 * c) = make_uint2(a0, b0);
   *reinterpret_cast<uint2*>(row + 2 * BK + 2 * c) = make_uint2(a1, b1);
   *reinterpret_cast<uint2*>(row + 4 * BK + 2 * c) = make_uint2(a2, b2);
@@ -94,7 +72,7 @@ __device__ __forceinline__ void offs_x(OffsX<BS>& o, const GemmArgs& g, int64_t 
 #pragma unroll
     for (int i = 0; i < BCH; ++i) {
       const int ch = tid + 64 * NWX * i, row = ch / 12, cc = ch - 12 * row;
-      o.b[i] = (uint32_t)((n_base / BN) * kb * (BN * LIMB_ROW * 2) + (cc >> 2) * (BN * BK * 2) + row * (BK * 2) +
+      o.b[i] = (uint32_t)((n_base / BN) * kb * (LGX_X3_BLOCK * 2) + (cc >> 2) * (LGX_X3_PLANE * 2) + row * (BK * 2) +
                           (((cc & 3) ^ ((row >> 2) & 3)) << 4));
     }
   } else {
@@ -112,7 +90,8 @@ __device__ __forceinline__ void load_x(StageX<BS>& st, const GemmArgs& g, int z,
   for (int i = 0; i < Cfg<NWX>::NL; ++i) st.a[i] = *reinterpret_cast<const float4*>(Ab + (uint32_t)((o.a[i] + kc) * 4u));
   if constexpr (BS) {
     const int kb = (K + BK - 1) / BK;
-    const char* Bb = reinterpret_cast<const char*>(g.Bs) + (int64_t)z * g.N * kb * (LIMB_ROW * 2) + t * (BN * LIMB_ROW * 2);
+    const char* Bb =
+        reinterpret_cast<const char*>(g.Bs) + (int64_t)z * g.N * kb * (LGX_X3_UNIT * 2) + t * (LGX_X3_BLOCK * 2);
 #pragma unroll
     for (int i = 0; i < BCH; ++i) st.b[i] = *reinterpret_cast<const uint4*>(Bb + o.b[i]);
   } else {
@@ -168,20 +147,10 @@ __device__ __forceinline__ void x3_read(X3Frag& f, const char* __restrict__ la, 
 // (e & 3)] - every lane holds runs of 4 consecutive columns of one row, stored as 16-byte
 // vectors by the epilogue (a quarter of the store instructions of the column layout).
 __device__ __forceinline__ void x3_mma(const X3Frag& f, Acc<NWX>& acc) {
-  // small terms first (they are the ones the accumulator's rounding would otherwise swamp last)
 #pragma unroll
   for (int i = 0; i < Cfg<NWX>::WI; ++i)
 #pragma unroll
-    for (int j = 0; j < Cfg<NWX>::WJ; ++j) {
-      f32x16 c = acc[i][j];
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.b[j][2], f.a[i][0], c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.b[j][1], f.a[i][1], c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.b[j][0], f.a[i][2], c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.b[j][1], f.a[i][0], c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.b[j][0], f.a[i][1], c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.b[j][0], f.a[i][0], c, 0, 0, 0);
-      acc[i][j] = c;
-    }
+    for (int j = 0; j < Cfg<NWX>::WJ; ++j) acc[i][j] = lgx_split_mma<true>(acc[i][j], f.b[j], f.a[i]);
 }
 
 __device__ __forceinline__ float4 q4(const f32x16& v, int q) {
@@ -368,7 +337,7 @@ __global__ void __launch_bounds__(64 * NWX, 2) gemm_nt_x3_kernel(GemmArgs g) {
 
 // ---------------------------------------------------------------------------------------- weights
 // Pre-split operand: out[b][n][k] = transpose ? src[b][k][n] : src[b][n][k] as RNE bf16 limbs in
-// the layout the kernel copies, dst[b*dst_bs + n*dst_ld + (k/32)*96 + limb*32 + k%32], zero for
+// the image the kernels copy, dst[b * dst_bs + x3_limb_off(n, k, limb)] (lgx_split_bf16.h), zero for
 // k >= K up to the 32-k block.  One thread per (b, n, k).
 struct SplitJobs {
   lgx_copy2d_job job[LGX_MAX_REDUCE_JOBS];
@@ -393,11 +362,7 @@ __global__ void __launch_bounds__(256) split_rows_kernel(SplitJobs J) {
   float x = 0.f;
   if (k < kout) x = jb.src[b * jb.src_bs + (tr ? (int64_t)k * jb.src_ld + n : (int64_t)n * jb.src_ld + k)];
   uint16_t* d = reinterpret_cast<uint16_t*>(jb.dst) + b * jb.dst_bs + x3_limb_off(n, k, 0, kp / BK);
-  uint32_t l0, l1, l2;
-  split2(x, 0.f, l0, l1, l2);
-  d[0] = (uint16_t)l0;                 // limb l at + l * 128 * 32 (x3_limb_off)
-  d[BN * BK] = (uint16_t)l1;
-  d[2 * BN * BK] = (uint16_t)l2;
+  lgx_split1(x, d[0], d[LGX_X3_PLANE], d[2 * LGX_X3_PLANE]);
 }
 
 }  // namespace
@@ -412,24 +377,15 @@ int lgx_gemm_nt_split(const lgx_gemm_args& a, int cus, void* stream_) {
   GemmArgs g{a.M, a.N, a.K, a.batch, a.epi, a.A, a.lda, a.sa, a.B, a.ldb, a.sb, a.C, a.ldc, a.sc, a.bias, a.Y,
              a.partials, 0, a.Bs};
   const int64_t tiles = ((a.M + BM - 1) / BM) * (a.N / BN) * a.batch;
-  static const bool attrs = [] {
-    bool ok = true;
-    const void* ks[] = {reinterpret_cast<const void*>(&gemm_nt_x3_kernel<LGX_GEMM_PLAIN, false>),
-                        reinterpret_cast<const void*>(&gemm_nt_x3_kernel<LGX_GEMM_BIAS_ELU, false>),
-                        reinterpret_cast<const void*>(&gemm_nt_x3_kernel<LGX_GEMM_DELU_COLSUM, false>),
-                        reinterpret_cast<const void*>(&gemm_nt_x3_kernel<LGX_GEMM_PLAIN, true>),
-                        reinterpret_cast<const void*>(&gemm_nt_x3_kernel<LGX_GEMM_BIAS_ELU, true>),
-                        reinterpret_cast<const void*>(&gemm_nt_x3_kernel<LGX_GEMM_DELU_COLSUM, true>)};
-    for (const void* k : ks) ok &= hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, X3_LDS) == hipSuccess;
-    return ok;
-  }();
+  static const bool attrs = lgx_allow_dynamic_lds(
+      {&gemm_nt_x3_kernel<LGX_GEMM_PLAIN, false>, &gemm_nt_x3_kernel<LGX_GEMM_BIAS_ELU, false>,
+       &gemm_nt_x3_kernel<LGX_GEMM_DELU_COLSUM, false>, &gemm_nt_x3_kernel<LGX_GEMM_PLAIN, true>,
+       &gemm_nt_x3_kernel<LGX_GEMM_BIAS_ELU, true>, &gemm_nt_x3_kernel<LGX_GEMM_DELU_COLSUM, true>},
+      X3_LDS);
   if (!attrs) return lgx_fail(LGX_EHIP, "lgx_gemm_nt: hipFuncSetAttribute (dynamic LDS) failed");
-  if (a.Bs && (((uintptr_t)a.Bs & 15) || (int64_t)a.N * ((a.K + BK - 1) / BK) * (LIMB_ROW * 2) >= (1ll << 31)))
+  if (a.Bs && (((uintptr_t)a.Bs & 15) || x3_image_elems(a.N, a.K) * 2 >= (1ll << 31)))
     return lgx_fail(LGX_EINVAL, "lgx_gemm_nt: pre-split B must be 16-byte aligned and < 2 GB per batch entry");
-  // persistent: 2 workgroups per CU (53 KB of LDS each), a multiple of 8 (XCD tile ranges)
-  const int64_t per_xcd = (tiles + 7) / 8;
-  const int64_t wgs = 8 * std::min<int64_t>(per_xcd, std::max(1, 2 * cus / 8));
-  const dim3 grid((unsigned)wgs), block(64 * NWX);
+  const dim3 grid((unsigned)lgx_xcd_grid(tiles, cus, 2)), block(64 * NWX);   // 53 KB of LDS: 2 workgroups per CU
 #define LGX_X3(EPI, BS) LGX_LAUNCH((gemm_nt_x3_kernel<EPI, BS>), grid, block, X3_LDS, stream, g)
   if (a.Bs) {
     if (a.epi == LGX_GEMM_BIAS_ELU) LGX_X3(LGX_GEMM_BIAS_ELU, true);
@@ -444,7 +400,7 @@ int lgx_gemm_nt_split(const lgx_gemm_args& a, int cus, void* stream_) {
   return lgx_hip_status("lgx_gemm_nt");
 }
 
-extern "C" int64_t lgx_split_bf16_elems(int32_t n, int32_t k) { return (int64_t)n * ((k + BK - 1) / BK) * LIMB_ROW; }
+extern "C" int64_t lgx_split_bf16_elems(int32_t n, int32_t k) { return x3_image_elems(n, k); }
 
 extern "C" int lgx_split_bf16(const lgx_copy2d_job* jobs, int32_t njobs, void* stream) {
   if (!jobs || njobs <= 0 || njobs > LGX_MAX_REDUCE_JOBS) return lgx_fail(LGX_EINVAL, "lgx_split_bf16: bad job count");

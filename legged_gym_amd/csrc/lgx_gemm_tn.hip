@@ -4,9 +4,8 @@
 // i.e. dW_k = dZ_k^T Y_{k-1} per network z (actor, critic) and row slice s; lgx_reduce_slices sums
 // the slices into the flat gradient.  Replaces the library f32 bmm over slices.
 //
-// Same f32-accurate arithmetic as the split-bf16 path of lgx_gemm_nt (lgx_gemm_split.hip): both
-// operands split into three RNE bf16 limbs, six limb products on v_mfma_f32_32x32x16_bf16 (a single
-// product within 2^-21 |a b| on each of the six kernels below: tests/test_gpu_split_products.py).
+// Same f32-accurate arithmetic as the split-bf16 path of lgx_gemm_nt (lgx_split_bf16.h), on each of
+// the six kernels below.
 // Both operands are row-major in m (the reduction index), so the MFMA fragments (8 consecutive m
 // of one column per lane) are column reads of the staged tiles:
 //   * each 32-row stage of A (128 columns n) and B (128 columns c) is loaded as f32 (16-byte row
@@ -38,14 +37,14 @@
 #include <type_traits>
 
 #include "lgx_internal.h"
+#include "lgx_launch.h"
+#include "lgx_split_bf16.h"
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+using bf16x8 = lgx_bf16x8;
+using f32x16 = lgx_f32x16;
 typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef float fx2 __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int TT = 128;                   // output tile columns (c); rows (n): RA = 128 | 256
 constexpr int TK = 32;                    // rows m per stage
@@ -82,18 +81,14 @@ struct TnArgs {
   int32_t rt, ct, tiles;
 };
 
-__device__ __forceinline__ void split2(float x0, float x1, uint32_t& l0, uint32_t& l1, uint32_t& l2) {
-  lgx_split2(x0, x1, l0, l1, l2);   // (lgx_internal.h)
-}
-
 // staged row (m, column quad cq) of one operand into its limb image [limb][ROWS m][W cols]: split,
 // three 8-byte stores; the 8-byte unit cq of row m sits at cq ^ 8 (m & 3)
 template <int W, int ROWS = TK>
 __device__ __forceinline__ void tn_store_row(char* img, const float4& v, int cq, int m) {
   uint2 l0, l1, l2;
 #ifndef TN_NO_SPLIT
-  split2(v.x, v.y, l0.x, l1.x, l2.x);
-  split2(v.z, v.w, l0.y, l1.y, l2.y);
+  lgx_split2(v.x, v.y, l0.x, l1.x, l2.x);
+  lgx_split2(v.z, v.w, l0.y, l1.y, l2.y);
 #else   // A/B: raw bits (wrong results; measures the split's VALU cost)
   l0 = make_uint2(__float_as_uint(v.x), __float_as_uint(v.y));
   l1 = make_uint2(__float_as_uint(v.z), __float_as_uint(v.w));
@@ -250,14 +245,7 @@ __global__ void __launch_bounds__(64 * NWV, 1) gemm_tn_x3_kernel(TnArgs g) {
         for (int i = 0; i < 2; ++i)
 #pragma unroll
           for (int j = 0; j < 2; ++j) {
-            f32x16 c = acc[i][j];
-            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[hs % FB][i][2], fb[hs % FB][j][0], c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[hs % FB][i][1], fb[hs % FB][j][1], c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[hs % FB][i][0], fb[hs % FB][j][2], c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[hs % FB][i][1], fb[hs % FB][j][0], c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[hs % FB][i][0], fb[hs % FB][j][1], c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[hs % FB][i][0], fb[hs % FB][j][0], c, 0, 0, 0);
-            acc[i][j] = c;
+            acc[i][j] = lgx_split_mma<true>(acc[i][j], fa[hs % FB][i], fb[hs % FB][j]);
             side(4 * hs + 2 * i + j);
             __builtin_amdgcn_sched_barrier(0);   // keep each unit between its MFMA blocks
           }
@@ -413,16 +401,7 @@ __device__ __forceinline__ void tn_ws_consumer(const TnArgs& g, char* tlds, int 
           if (hs == 0 && j == 1) read_a(1, 1);
           __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-          for (int i = 0; i < WI; ++i) {
-            f32x16 c = acc[i][j];
-            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[hs][i][2], fb[cb][0], c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[hs][i][1], fb[cb][1], c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[hs][i][0], fb[cb][2], c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[hs][i][1], fb[cb][0], c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[hs][i][0], fb[cb][1], c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[hs][i][0], fb[cb][0], c, 0, 0, 0);
-            acc[i][j] = c;
-          }
+          for (int i = 0; i < WI; ++i) acc[i][j] = lgx_split_mma<true>(acc[i][j], fa[hs][i], fb[cb]);
           __builtin_amdgcn_sched_barrier(0);
         }
 #ifdef TN_WS_CLOCK
@@ -715,14 +694,7 @@ __global__ void __launch_bounds__(512, 1) gemm_tn_ring_kernel(TnArgs g) {
       for (int i = 0; i < WI; ++i)
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-          f32x16 c = acc[i][j];
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][2], fb[j][0], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][1], fb[j][1], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][0], fb[j][2], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][1], fb[j][0], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][0], fb[j][1], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][0], fb[j][0], c, 0, 0, 0);
-          acc[i][j] = c;
+          acc[i][j] = lgx_split_mma<true>(acc[i][j], fa[i], fb[j]);
           side(2 * i + j);
           if (WI == 2 && i == 1 && j == 1) {   // the last block (no side unit): stage k + 1's block-0
             pre_a(tlds + off_n, 0);   // fragments, dead since block (1, 0), two reads per MFMA (104 /
@@ -857,24 +829,14 @@ extern "C" int lgx_gemm_tn(const lgx_gemm_tn_args* args, void* stream) {
   const int64_t tiles = (int64_t)g.rt * g.ct * a.slices * a.batch;
   if (tiles >= (1ll << 31) / 8) return lgx_fail(LGX_EINVAL, "lgx_gemm_tn: too many tiles");
   g.tiles = (int32_t)tiles;
-  static const bool attrs =
-      hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_x3_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          TC<4>::LDS) == hipSuccess &&
-      hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_x3_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          TC<8>::LDS) == hipSuccess &&
-      hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_ws_kernel<256>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          TW<256>::LDS) == hipSuccess &&
-      hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_ws_kernel<128>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          TW<128>::LDS) == hipSuccess &&
-      hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_ring_kernel<256>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          TRing<256>::LDS) == hipSuccess &&
-      hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_ring_kernel<128>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          TRing<128>::LDS) == hipSuccess;
+  static const bool attrs = lgx_allow_dynamic_lds({&gemm_tn_x3_kernel<4>}, TC<4>::LDS) &&
+                            lgx_allow_dynamic_lds({&gemm_tn_x3_kernel<8>}, TC<8>::LDS) &&
+                            lgx_allow_dynamic_lds({&gemm_tn_ws_kernel<256>}, TW<256>::LDS) &&
+                            lgx_allow_dynamic_lds({&gemm_tn_ws_kernel<128>}, TW<128>::LDS) &&
+                            lgx_allow_dynamic_lds({&gemm_tn_ring_kernel<256>}, TRing<256>::LDS) &&
+                            lgx_allow_dynamic_lds({&gemm_tn_ring_kernel<128>}, TRing<128>::LDS);
   if (!attrs) return lgx_fail(LGX_EHIP, "lgx_gemm_tn: hipFuncSetAttribute (dynamic LDS) failed");
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  const int64_t per_xcd = (tiles + 7) / 8;
-  const int64_t wgs = 8 * std::min<int64_t>(per_xcd, std::max(1, cus / 8));
+  const int64_t wgs = lgx_xcd_grid(tiles, lgx_cu_count(), 1);   // one workgroup per CU
   if (ring)
     LGX_LAUNCH(gemm_tn_ring_kernel<256>, dim3((unsigned)wgs), dim3(512), TRing<256>::LDS, reinterpret_cast<hipStream_t>(stream), g);
   else if (ring128)

@@ -1,11 +1,10 @@
 // Pipelined split-bf16 GEMM of the PPO update (lgx_gemm_nt with a pre-split B operand):
 //   C[z][m][n] = epi( sum_k A[z][m][k] * B[z][n][k] ),  K % 32 == 0, N % 128 == 0.
 //
-// Same arithmetic as gemm_nt_x3_kernel (lgx_gemm_split.hip: three RNE bf16 limbs per f32
-// operand, the six limb products of order <= 2 on v_mfma_f32_32x32x16_bf16, f32 accumulation),
-// restructured around the load pipeline, which is what bounded that kernel: with one K stage of
-// register-staged prefetch and a barrier pair per 32-k stage, its loads were exposed once per
-// stage (measured: the kernel without its MFMAs took as long as the MFMA floor).
+// Same arithmetic as gemm_nt_x3_kernel (lgx_split_bf16.h), restructured around the load pipeline,
+// which is what bounded that kernel: with one K stage of register-staged prefetch and a barrier
+// pair per 32-k stage, its loads were exposed once per stage (measured: the kernel without its
+// MFMAs took as long as the MFMA floor).
 //
 //   * 256 x 128 output tile per workgroup; one workgroup per CU (149 KB of LDS), persistent over
 //     XCD-contiguous tile ranges (consecutive tiles share A rows: L2 reuse on one XCD).  Wave
@@ -40,16 +39,10 @@
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float fx2 __attribute__((ext_vector_type(2)));
-typedef float f32x16v __attribute__((ext_vector_type(16)));
-
-constexpr int PN = 128, PK = 32;
+constexpr int PN = LGX_X3_BN, PK = LGX_X3_BK;   // a tile's columns x a slot's k: one pre-split B block
 constexpr int LGX_X3P_MAX_LDS = 160 * 1024;   // LDS per CU (one workgroup per CU)
-constexpr int B_ST = 3 * PN * PK * 2;        // 24 KB: limb B stage ([limb][128 n][64 B])
+constexpr int B_ST = LGX_X3_BLOCK * 2;       // 24 KB: limb B stage ([limb][128 n][64 B]), a block verbatim
 constexpr int NSA = 3, NSB = 2;              // ring depths
-constexpr int B_BLK = 3 * 128 * 32;             // bf16 per pre-split (128 n x 32 k) block
 
 // X3P_WGN: waves along N of the 8-wave 256-row tile.  1 (default): 8 x 1 waves of 32 x 128, each
 // wave splits only its own 32 A rows (the 4 x 2 layout of 64 x 64 waves split every A row in
@@ -136,16 +129,12 @@ __device__ __forceinline__ void p_barrier() {
   asm volatile("" ::: "memory");
 }
 
-__device__ __forceinline__ void split2(float x0, float x1, uint32_t& l0, uint32_t& l1, uint32_t& l2) {
-  lgx_split2(x0, x1, l0, l1, l2);   // (lgx_internal.h)
-}
-
 __device__ __forceinline__ void split8(const float4& x, const float4& y, bf16x8 (&o)[3]) {
   uint4 u0, u1, u2;
-  split2(x.x, x.y, u0.x, u1.x, u2.x);
-  split2(x.z, x.w, u0.y, u1.y, u2.y);
-  split2(y.x, y.y, u0.z, u1.z, u2.z);
-  split2(y.z, y.w, u0.w, u1.w, u2.w);
+  lgx_split2(x.x, x.y, u0.x, u1.x, u2.x);
+  lgx_split2(x.z, x.w, u0.y, u1.y, u2.y);
+  lgx_split2(y.x, y.y, u0.z, u1.z, u2.z);
+  lgx_split2(y.z, y.w, u0.w, u1.w, u2.w);
   o[0] = __builtin_bit_cast(bf16x8, u0);
   o[1] = __builtin_bit_cast(bf16x8, u1);
   o[2] = __builtin_bit_cast(bf16x8, u2);
@@ -213,7 +202,8 @@ __device__ __forceinline__ DmaPlan plan_b(uint32_t lds0, int buf, const PArgs& g
   using X = XC<NWV, PM>;
   constexpr int BG = X::B_GL;
   (void)BG;
-  return DmaPlan{uniform_ptr(reinterpret_cast<const char*>(g.Bs + T.z * g.sbs + (int64_t)(T.nt * g.kb + ks) * B_BLK) +
+  return DmaPlan{uniform_ptr(reinterpret_cast<const char*>(g.Bs + T.z * g.sbs +
+                                                           (int64_t)(T.nt * g.kb + ks) * LGX_X3_BLOCK) +
                              X::bw_off(tid >> 6)),
                  (uint32_t)__builtin_amdgcn_readfirstlane(lds0 + X::OFF_B + buf * B_ST + X::bw_off(tid >> 6))};
 }
@@ -238,7 +228,7 @@ __device__ __forceinline__ void issue_b(uint32_t lds0, int buf, const PArgs& g, 
   using X = XC<NWV, PM>;
   constexpr int BG = X::B_GL;
   const int w = tid >> 6, lane = tid & 63;
-  const char* src = uniform_ptr(g.Bs + T.z * g.sbs + (int64_t)(T.nt * g.kb + ks) * B_BLK);
+  const char* src = uniform_ptr(g.Bs + T.z * g.sbs + (int64_t)(T.nt * g.kb + ks) * LGX_X3_BLOCK);
   const uint32_t dst = __builtin_amdgcn_readfirstlane(lds0 + X::OFF_B + buf * B_ST + X::bw_off(w));
   if (!X::BOLD || __builtin_amdgcn_readfirstlane(w) < NWV / 2) {
 #pragma unroll
@@ -261,7 +251,7 @@ __device__ __forceinline__ void issue_b(uint32_t lds0, int buf, const PArgs& g, 
 // DMA loads of a 4-wave slot took ~950 cycles of the wave's ~5600).
 template <int NWV, int PM, bool TRANS, typename Side>
 __device__ __forceinline__ void compute_slot(const char* __restrict__ la, const char* __restrict__ lb, int wm, int wn,
-                                             int r, int h, f32x16v (&acc)[XC<NWV, PM>::WI][XC<NWV, PM>::WJ],
+                                             int r, int h, f32x16 (&acc)[XC<NWV, PM>::WI][XC<NWV, PM>::WJ],
                                              Side&& side) {
   constexpr int WI = XC<NWV, PM>::WI, WJ = XC<NWV, PM>::WJ;
   const int sa = (r >> 1) & 7, sb = (r >> 2) & 3;
@@ -297,35 +287,21 @@ __device__ __forceinline__ void compute_slot(const char* __restrict__ la, const 
                         (float)b[j][1][3] + (float)b[j][2][5];
         continue;
 #endif
-        f32x16v c = acc[i][j];
-        if constexpr (TRANS) {   // weights first: lane = output row, 4 runs of 4 columns
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b[j][2], a[i][0], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b[j][1], a[i][1], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b[j][0], a[i][2], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b[j][1], a[i][0], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b[j][0], a[i][1], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b[j][0], a[i][0], c, 0, 0, 0);
-        } else {                 // rows first: lane = output column (column sums in registers)
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][0], b[j][2], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][1], b[j][1], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][2], b[j][0], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][0], b[j][1], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][1], b[j][0], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][0], b[j][0], c, 0, 0, 0);
-        }
-        acc[i][j] = c;
+        // TRANS: weights first, lane = output row, 4 runs of 4 columns; else rows first, lane =
+        // output column (column sums in registers)
+        acc[i][j] = lgx_split_mma<TRANS>(acc[i][j], b[j], a[i]);
         side((s * WI + i) * WJ + j);
       }
   }
 }
 
-__device__ __forceinline__ float4 q4(const f32x16v& v, int q) {
+__device__ __forceinline__ float4 q4(const f32x16& v, int q) {
   return make_float4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
 }
 
 // Bias + ELU (or plain) output of float4 run gi = (i, j, q), gi = 4 (WJ i + j) + q, of a lane.
 template <int EPI, int NWV, int PM>
-__device__ __forceinline__ void p_store_group(const PArgs& g, const f32x16v (&pend)[XC<NWV, PM>::WI][XC<NWV, PM>::WJ],
+__device__ __forceinline__ void p_store_group(const PArgs& g, const f32x16 (&pend)[XC<NWV, PM>::WI][XC<NWV, PM>::WJ],
                                               const PTile& T, int wm, int wn, int r, int h, const float* bias_lds,
                                               int gi) {
   constexpr int WI = XC<NWV, PM>::WI, WJ = XC<NWV, PM>::WJ;
@@ -367,7 +343,7 @@ __device__ __forceinline__ float4 delu_load(const PArgs& g, const PTile& T, int 
 
 
 template <int NWV, int PM>
-__device__ __forceinline__ void delu_apply(int gi, const float4& y, f32x16v (&pend)[XC<NWV, PM>::WI][XC<NWV, PM>::WJ]) {
+__device__ __forceinline__ void delu_apply(int gi, const float4& y, f32x16 (&pend)[XC<NWV, PM>::WI][XC<NWV, PM>::WJ]) {
   constexpr int WJ = XC<NWV, PM>::WJ;
   const int q = gi & 3, j = (gi >> 2) % WJ, i = (gi >> 2) / WJ;
   pend[i][j][4 * q] *= elu_grad_from_out(y.x);
@@ -379,7 +355,7 @@ __device__ __forceinline__ void delu_apply(int gi, const float4& y, f32x16v (&pe
 // every run of a tile at once (the last tile, or the runtime-K kernels): all Y loads in flight,
 // then multiply and store
 template <int NWV, int PM>
-__device__ __forceinline__ void delu_tile(const PArgs& g, f32x16v (&acc)[XC<NWV, PM>::WI][XC<NWV, PM>::WJ],
+__device__ __forceinline__ void delu_tile(const PArgs& g, f32x16 (&acc)[XC<NWV, PM>::WI][XC<NWV, PM>::WJ],
                                           const PTile& T, int wm, int wn, int r, int h) {
   constexpr int GROUPS = XC<NWV, PM>::GROUPS;
   float4 y[GROUPS];
@@ -398,7 +374,7 @@ __device__ __forceinline__ void delu_tile(const PArgs& g, f32x16v (&acc)[XC<NWV,
 // across the lane halves and, in a fixed order, across the waves of each 128-row partial block
 // (partials[m / 128][z][n], the layout of gemm_nt_x3_kernel's).  scratch: [NWV][128] floats.
 template <int NWV, int PM>
-__device__ __forceinline__ void delu_epilogue(const PArgs& g, const f32x16v (&acc)[XC<NWV, PM>::WI][XC<NWV, PM>::WJ],
+__device__ __forceinline__ void delu_epilogue(const PArgs& g, const f32x16 (&acc)[XC<NWV, PM>::WI][XC<NWV, PM>::WJ],
                                               const PTile& T, int wave, int wm, int wn, int r, int h,
                                               float* scratch) {
   using X = XC<NWV, PM>;
@@ -543,7 +519,7 @@ __global__ void __launch_bounds__(64 * NWV, 1) gemm_nt_x3p_kernel(PArgs g) {
     next_a();
   }
 
-  f32x16v acc[WI][WJ], pend[WI][WJ];
+  f32x16 acc[WI][WJ], pend[WI][WJ];
 #pragma unroll
   for (int i = 0; i < WI; ++i)
 #pragma unroll
@@ -573,8 +549,8 @@ __global__ void __launch_bounds__(64 * NWV, 1) gemm_nt_x3p_kernel(PArgs g) {
   (void)BG0;
   uint32_t off_ac = 0, off_ai = 2 * A_ST;   // A ring byte offsets of slot q (compute) and q + 2 (issue)
   const char* a_nxt = uniform_ptr(reinterpret_cast<const char*>(g.A + T.z * g.sa));
-  const char* b_nxt = uniform_ptr(reinterpret_cast<const char*>(g.Bs + T.z * g.sbs + (int64_t)(T.nt * g.kb) * B_BLK) +
-                                  X::bw_off(tid >> 6));
+  const char* b_nxt = uniform_ptr(
+      reinterpret_cast<const char*>(g.Bs + T.z * g.sbs + (int64_t)(T.nt * g.kb) * LGX_X3_BLOCK) + X::bw_off(tid >> 6));
   for (int32_t tj = 0; tj < ntiles; ++tj) {
     if (KBT == 0) T = ptile(g, t0 + tj * stride);
     PTile Tn = T;
@@ -585,8 +561,8 @@ __global__ void __launch_bounds__(64 * NWV, 1) gemm_nt_x3p_kernel(PArgs g) {
       Tn = ptile(g, t0 + (tj + 1) * stride);   // (past the last tile: bases computed, never loaded)
       if (!last_tile) a_offs<NWV, PM>(aon, g, Tn.mt, tid);
       a_nxt = uniform_ptr(reinterpret_cast<const char*>(g.A + Tn.z * g.sa));
-      b_nxt = uniform_ptr(reinterpret_cast<const char*>(g.Bs + Tn.z * g.sbs + (int64_t)(Tn.nt * g.kb) * B_BLK) +
-                          X::bw_off(tid >> 6));
+      b_nxt = uniform_ptr(
+          reinterpret_cast<const char*>(g.Bs + Tn.z * g.sbs + (int64_t)(Tn.nt * g.kb) * LGX_X3_BLOCK) + X::bw_off(tid >> 6));
     }
 #pragma unroll UNR
     for (int k = 0; k < kb; ++k, ++q) {
@@ -617,7 +593,7 @@ __global__ void __launch_bounds__(64 * NWV, 1) gemm_nt_x3p_kernel(PArgs g) {
       DmaPlan pb{nullptr, 0}, pa{nullptr, 0};
       const PTile Tbias = KBT > 0 ? (b_next ? Tn : T) : Tb;
       if constexpr (KBT > 0) {   // (KBT even: the B ring index (q + 1) % 2 is (k + 1) % 2)
-        pb = DmaPlan{(b_next ? b_nxt : b_cur) + ((k + 1) % KBT) * (B_BLK * 2), lds_bw + ((k + 1) % NSB) * B_ST};
+        pb = DmaPlan{(b_next ? b_nxt : b_cur) + ((k + 1) % KBT) * (LGX_X3_BLOCK * 2), lds_bw + ((k + 1) % NSB) * B_ST};
         pa = DmaPlan{(a_next ? a_nxt : a_cur) + ((k + 2) % KBT) * (PK * 4), lds_aw + off_ai};
       } else {
         if (do_b) pb = plan_b<NWV, PM>(lds0, (q + 1) % NSB, g, Tbias, kbb, tid);
@@ -784,13 +760,8 @@ struct X3PTable {
 
 template <int NWV, int PM>
 bool x3p_attrs() {
-  bool ok = true;
-  for (const auto& row : X3PTable<NWV, PM>::k)
-    for (x3p_fn f : row)
-      if (f)
-        ok &= hipFuncSetAttribute(reinterpret_cast<const void*>(f), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  LGX_X3P_MAX_LDS) == hipSuccess;
-  return ok;
+  using T = X3PTable<NWV, PM>;
+  return lgx_allow_dynamic_lds(&T::k[0][0], sizeof(T::k) / sizeof(x3p_fn), LGX_X3P_MAX_LDS);
 }
 
 // Dynamic LDS of an instantiation: the rings + bias / scratch area, or for the deferred
@@ -831,7 +802,7 @@ int lgx_gemm_nt_x3p(const lgx_gemm_args& a, int cus, void* stream_) {
   g.lda = a.lda;
   g.sa = a.sa;
   g.Bs = a.Bs;
-  g.sbs = (int64_t)a.N * g.kb * 96;
+  g.sbs = x3_image_elems(a.N, a.K);
   g.C = a.C;
   g.ldc = a.ldc;
   g.sc = a.sc;
@@ -857,9 +828,7 @@ int lgx_gemm_nt_x3p(const lgx_gemm_args& a, int cus, void* stream_) {
   const int ki = kbt == 0 ? 0 : kbt == 4 ? 1 : kbt == 8 ? 2 : 3;
   const x3p_fn f = pm == 128 ? X3PTable<8, 128>::k[a.epi][ki] : X3PTable<8, 256>::k[a.epi][ki];
   const int lds = pm == 128 ? x3p_lds<8, 128>(a.epi, kbt) : x3p_lds<8, 256>(a.epi, kbt);
-  // persistent: one workgroup per CU, a multiple of 8 (XCD tile ranges)
-  const int64_t per_xcd = (g.tiles + 7) / 8;
-  const int64_t wgs = 8 * std::min<int64_t>(per_xcd, std::max(1, cus / 8));
-  LGX_LAUNCH(f, dim3((unsigned)wgs), dim3(64 * nwv), lds, stream, g);
+  // persistent: one workgroup per CU
+  LGX_LAUNCH(f, dim3((unsigned)lgx_xcd_grid(g.tiles, cus, 1)), dim3(64 * nwv), lds, stream, g);
   return lgx_hip_status("lgx_gemm_nt");
 }

@@ -162,17 +162,6 @@ extern thread_local lgx_timing_slot lgx_timing;
     }                                                                                            \
   } while (0)
 
-// Pre-split (split-bf16) GEMM operand layout: the LDS image of every 128-column x 32-k block,
-// [n / 128][k / 32][limb][n % 128][32 k], the four 16-byte k-chunks of a 64-byte row stored at
-// chunk ^ ((n >> 2) & 3) so the 32x32x16 fragment reads (ds_read_b128) are bank-conflict free.
-// Offset (bf16 units) of element (n, k) limb `limb` within one batch entry; kb = ceil(K / 32).
-// One batch entry holds N * kb * 96 elements (lgx_split_bf16_elems); N % 128 == 0.
-__host__ __device__ inline int64_t x3_limb_off(int n, int k, int limb, int kb) {
-  const int nn = n & 127, kk = k & 31;
-  return ((int64_t)((n >> 7) * kb + (k >> 5)) * 3 + limb) * (128 * 32) + nn * 32 +
-         ((((kk >> 3) ^ ((nn >> 2) & 3))) << 3) + (kk & 7);
-}
-
 // error reporting shared by the translation units (thread-local message, lgx_last_error)
 int lgx_fail(int code, const char* msg);
 // lgx_gemm_split.hip: the split-bf16 path of lgx_gemm_nt (arguments already checked)
@@ -209,22 +198,6 @@ __device__ __forceinline__ float lgx_ppo_logp_term(float d, float sd) {
 #pragma clang fp contract(off)
   const float half_log_2pi = 0.91893853320467274178f;
   return -(d * d) / (2.f * sd * sd) - logf(sd) - half_log_2pi;
-}
-// Three RNE bf16 limbs of two f32 values, packed (low half = first value): x = l0 + l1 + l2 + e,
-// |e| <= 2^-24 |x|; both subtractions are exact.  The split-bf16 GEMMs' operand split (lgx_gemm_x3p
-// / _tn / _split, lgx_mlp_x3).  (Round 6 measured the residuals as v_dot2c_f32_bf16 with a -1 in the
-// limb's half - 7 VALU per pair instead of 11, bitwise the same limbs - and the PPO update was
-// slower, 10.83 vs 10.46 ms, same box, alternated: the dot instruction does not issue at the rate of
-// the shift / subtract it replaces.)
-typedef __bf16 lgx_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float lgx_fx2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void lgx_split2(float x0, float x1, uint32_t& l0, uint32_t& l1, uint32_t& l2) {
-  l0 = __builtin_bit_cast(uint32_t, __builtin_convertvector((lgx_fx2){x0, x1}, lgx_bf16x2));
-  float r0 = x0 - __uint_as_float(l0 << 16), r1 = x1 - __uint_as_float(l0 & 0xffff0000u);
-  l1 = __builtin_bit_cast(uint32_t, __builtin_convertvector((lgx_fx2){r0, r1}, lgx_bf16x2));
-  r0 -= __uint_as_float(l1 << 16);
-  r1 -= __uint_as_float(l1 & 0xffff0000u);
-  l2 = __builtin_bit_cast(uint32_t, __builtin_convertvector((lgx_fx2){r0, r1}, lgx_bf16x2));
 }
 // PPO.process_env_step's time-out bootstrap: rew + gamma * (V * time_out), as torch evaluates it
 __device__ __forceinline__ float lgx_ppo_reward(float rew, float gamma, float value, bool time_out) {

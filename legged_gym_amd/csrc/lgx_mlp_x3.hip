@@ -1,10 +1,8 @@
 // Fused MLP forward on split-bf16 MFMA for the rollout's actor and critic (rsl_rl
 // ActorCritic.act / evaluate, obs-512-256-128-{12,1} with ELU: the per-env-step policy
 // inference of OnPolicyRunner.learn's rollout loop), both networks in ONE launch (blockIdx.y).
-// Same arithmetic as the PPO-update GEMMs (lgx_gemm_split.hip): every f32 operand as three RNE
-// bf16 limbs, the six limb products of order <= 2 on v_mfma_f32_32x32x16_bf16 with f32
-// accumulation (f32-accurate: a single product within 2^-21 |a b|, tests/test_gpu_split_products.py);
-// 2.67x the product rate of lgx_mlp_forward_kernel's f32 MFMA.
+// Same f32-accurate arithmetic as the PPO-update GEMMs (lgx_split_bf16.h); 2.67x the product rate of
+// lgx_mlp_forward_kernel's f32 MFMA.
 //
 //   * 32 rows per workgroup, 8 waves.  The rows' activations stay in LDS across all layers as
 //     bf16 limb images [limb][32 rows][Kp] (Kp = width rounded up to 64, 16-byte row pad), split
@@ -26,13 +24,13 @@
 
 #include "lgx_device.h"
 #include "lgx_internal.h"
+#include "lgx_launch.h"
+#include "lgx_split_bf16.h"
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float fx2 __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using bf16x8 = lgx_bf16x8;
+using f32x16 = lgx_f32x16;
 
 constexpr int XM_BM = 32;           // rows per workgroup
 constexpr int XM_NW = 8;            // waves per workgroup
@@ -72,10 +70,6 @@ struct XmAct {
   lgx_ppo_store_args s;
   int32_t store;
 };
-
-__device__ __forceinline__ void split2(float x0, float x1, uint32_t& l0, uint32_t& l1, uint32_t& l2) {
-  lgx_split2(x0, x1, l0, l1, l2);   // (lgx_internal.h)
-}
 
 template <int ACT>
 __device__ __forceinline__ float xm_act_c(float v) {
@@ -138,25 +132,17 @@ __device__ __forceinline__ void xm_layer(const char* __restrict__ img, int rs, c
 #pragma unroll
     for (int g = 0; g < G; ++g) {
       const char* pa = img + ao + (kb0 + g) * 32;
-      const bf16x8 a0 = *reinterpret_cast<const bf16x8*>(pa);
-      const bf16x8 a1 = *reinterpret_cast<const bf16x8*>(pa + limb_bytes);
-      const bf16x8 a2 = *reinterpret_cast<const bf16x8*>(pa + 2 * limb_bytes);
+      const bf16x8 a[3] = {*reinterpret_cast<const bf16x8*>(pa), *reinterpret_cast<const bf16x8*>(pa + limb_bytes),
+                           *reinterpret_cast<const bf16x8*>(pa + 2 * limb_bytes)};
 #pragma unroll
       for (int t = 0; t < TPW; ++t) {
         const bf16x8* w = b + (g * TPW + t) * 3;
-        f32x16 c = acc[t];   // small limb products first
 #ifdef XM_NO_MFMA   // A/B: weight stream + A reads only (wrong results)
-        c[0] += (float)w[2][0] + (float)w[1][1] + (float)w[0][2] + (float)a0[0] + (float)a1[1] + (float)a2[2];
-        acc[t] = c;
+        acc[t][0] +=
+            (float)w[2][0] + (float)w[1][1] + (float)w[0][2] + (float)a[0][0] + (float)a[1][1] + (float)a[2][2];
         continue;
 #endif
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w[2], a0, c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w[1], a1, c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w[0], a2, c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w[1], a0, c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w[0], a1, c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w[0], a0, c, 0, 0, 0);
-        acc[t] = c;
+        acc[t] = lgx_split_mma<true>(acc[t], w, a);   // the weights first
       }
     }
   };
@@ -244,7 +230,7 @@ __global__ void __launch_bounds__(XM_NT) lgx_mlp_x3_kernel(XmBatch batch, int32_
         if (i < total) {
           const int row = i / pairs, k = 2 * (i - row * pairs);
           uint32_t l0, l1, l2;
-          split2(v[u][0], v[u][1], l0, l1, l2);
+          lgx_split2(v[u][0], v[u][1], l0, l1, l2);
           char* p = img0 + row * rs + 2 * k;
           *reinterpret_cast<uint32_t*>(p) = l0;
           *reinterpret_cast<uint32_t*>(p + XM_BM * rs) = l1;
@@ -310,8 +296,8 @@ __global__ void __launch_bounds__(XM_NT) lgx_mlp_x3_kernel(XmBatch batch, int32_
 #pragma unroll
             for (int i = 0; i < 4; ++i) v[i] = xm_act_c<AC>(v[i]);
             uint32_t a0, a1, a2, b0, b1, b2;
-            split2(v[0], v[1], a0, a1, a2);
-            split2(v[2], v[3], b0, b1, b2);
+            lgx_split2(v[0], v[1], a0, a1, a2);
+            lgx_split2(v[2], v[3], b0, b1, b2);
             char* p = out + row * rs_out + 2 * c0;
             *reinterpret_cast<uint2*>(p) = make_uint2(a0, b0);
             *reinterpret_cast<uint2*>(p + XM_BM * rs_out) = make_uint2(a1, b1);
@@ -408,7 +394,7 @@ __device__ __forceinline__ void xm_split_one(const float* __restrict__ W, int N,
   const float v0 = (n < N && k < K) ? W[(int64_t)n * K + k] : 0.f;
   const float v1 = (n < N && k + 1 < K) ? W[(int64_t)n * K + k + 1] : 0.f;
   uint32_t l0, l1, l2;
-  split2(v0, v1, l0, l1, l2);
+  lgx_split2(v0, v1, l0, l1, l2);
   const int64_t base = ((int64_t)((n >> 5) * KB + (k >> 4)) * 3) * 512 + (n & 31) * 16 + (k & 15);
   uint32_t* d = reinterpret_cast<uint32_t*>(dst + base);
   d[0] = l0;
@@ -504,11 +490,7 @@ int mlp_x3_launch(const lgx_mlp_x3_desc* d, int32_t count, const XmAct* xa, void
     rows = std::max(rows, m.rows);
   }
   if (rows == 0) return LGX_OK;
-  static const bool attr =
-      hipFuncSetAttribute(reinterpret_cast<const void*>(&lgx_mlp_x3_kernel<false>),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, XM_LDS_MAX) == hipSuccess &&
-      hipFuncSetAttribute(reinterpret_cast<const void*>(&lgx_mlp_x3_kernel<true>),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, XM_LDS_MAX) == hipSuccess;
+  static const bool attr = lgx_allow_dynamic_lds({&lgx_mlp_x3_kernel<false>, &lgx_mlp_x3_kernel<true>}, XM_LDS_MAX);
   if (!attr) return lgx_fail(LGX_EHIP, "lgx_mlp_x3_forward: hipFuncSetAttribute (dynamic LDS) failed");
   const int64_t tiles = (rows + XM_BM - 1) / XM_BM;
   const int64_t grid = count == 2 ? 8 * ((tiles + 3) / 4) : tiles;

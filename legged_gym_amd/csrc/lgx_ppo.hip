@@ -22,6 +22,8 @@
 
 
 #include "lgx_internal.h"
+#include "lgx_launch.h"
+#include "lgx_split_bf16.h"
 
 namespace {
 
@@ -803,13 +805,6 @@ sumsq_kernel(const float* __restrict__ g, int64_t n, float scale, float* __restr
 // Mirrors: derived copies of parameter blocks that the next minibatch's GEMMs read (zero-padded
 // layer-1 weights, transposed hidden weights; lgx_copy2d job layout with src inside p) written
 // with the updated value, so no weight-preparation pass runs between minibatches.
-// round-to-nearest-even bf16 (as v_cvt_pk_bf16_f32, finite inputs)
-__device__ __forceinline__ uint16_t bf16_rne(float x) {
-  typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-  typedef float fx2_t __attribute__((ext_vector_type(2)));
-  return (uint16_t)__builtin_bit_cast(uint32_t, __builtin_convertvector((fx2_t){x, 0.f}, bf16x2_t));
-}
-
 struct Mirror {
   int64_t off, dst_ld, dst_bs;  // off: first flat index of the block in p
   float* dst;
@@ -832,12 +827,7 @@ __device__ __forceinline__ void mirror_store(const Mirror& J, int32_t b, int32_t
     const int32_t nn = (J.transpose & 1) ? cc : rr, kk = (J.transpose & 1) ? rr : cc;
     const int32_t kout = (J.transpose & 1) ? J.rows : J.cols;
     uint16_t* d = reinterpret_cast<uint16_t*>(J.dst) + b * J.dst_bs + x3_limb_off(nn, kk, 0, (kout + 31) >> 5);
-    const uint16_t l0 = bf16_rne(pi);
-    const float r1 = pi - __uint_as_float((uint32_t)l0 << 16);
-    const uint16_t l1 = bf16_rne(r1);
-    d[0] = l0;                   // limb l at + l * 128 * 32
-    d[4096] = l1;
-    d[8192] = bf16_rne(r1 - __uint_as_float((uint32_t)l1 << 16));
+    lgx_split1(pi, d[0], d[LGX_X3_PLANE], d[2 * LGX_X3_PLANE]);
   } else {
     J.dst[b * J.dst_bs + (J.transpose ? (int64_t)cc * J.dst_ld + rr : (int64_t)rr * J.dst_ld + cc)] = pi;
   }
@@ -1073,12 +1063,8 @@ extern "C" int lgx_ppo_loss_bwd(const lgx_ppo_loss_args* args, float* head_parti
   int64_t lay[3];
   lgx_ppo_loss_bwd_layout(a.rows, a.num_actions, a.hidden, lay);
   if (lay[2] > 96 * 1024) return lgx_fail(LGX_EINVAL, "lgx_ppo_loss_bwd: hidden too wide for the LDS row stage");
-  static const bool attr_ok = [] {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(&ppo_loss_bwd_kernel<12>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) == hipSuccess &&
-           hipFuncSetAttribute(reinterpret_cast<const void*>(&ppo_loss_bwd_kernel<LGX_PPO_MAX_ACTIONS>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) == hipSuccess;
-  }();
+  static const bool attr_ok =
+      lgx_allow_dynamic_lds({&ppo_loss_bwd_kernel<12>, &ppo_loss_bwd_kernel<LGX_PPO_MAX_ACTIONS>}, 96 * 1024);
   if (!attr_ok) return lgx_fail(LGX_EHIP, "lgx_ppo_loss_bwd: hipFuncSetAttribute failed");
   const int blocks = (int)((a.rows + LB_ROWS - 1) / LB_ROWS);
   // (LGX_LAUNCH on the call's last launch: a bound event, lgx_launch_bind_event, marks its end)

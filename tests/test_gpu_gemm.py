@@ -44,7 +44,7 @@ def _presplit(B, transpose=False):
 
 
 def _limb_index(nout, kout, device):
-    """x3_limb_off (lgx_internal.h): [3, nout, kb*32] offsets of the tiled pre-split layout."""
+    """x3_limb_off (lgx_split_bf16.h): [3, nout, kb*32] offsets of the tiled pre-split layout."""
     kb = -(-kout // 32)
     n = torch.arange(nout, device=device)[:, None]
     k = torch.arange(kb * 32, device=device)[None, :]
