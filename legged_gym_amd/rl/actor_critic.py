@@ -2,15 +2,23 @@
 built by OnPolicyRunner at task_registry.py:160; upstream rsl_rl v1.0.x `ActorCritic`).
 
 Training forward/backward uses torch autograd (library GEMMs).  The no-grad rollout forward
-(`act` under inference mode, `act_inference`, `evaluate`) runs on the lgx fused MLP kernel
-(f32 MFMA, all layers in one launch with the activations resident in LDS) when the module
-lives on a GPU; weights are re-transposed for the kernel lazily after each optimizer step.
+(`act` under inference mode, `act_inference`, `evaluate`) runs on the lgx fused MLP kernels
+(_FusedMLP: split-bf16 MFMA by default; all layers in one launch with the activations resident in LDS)
+when the module lives on a GPU; the kernels' weight images are rebuilt lazily after each optimizer step.
 """
 import ctypes as C
+import os
 
 import torch
 import torch.nn as nn
 from torch.distributions import Normal
+
+from legged_gym_amd.sim import abi
+from legged_gym_amd.sim import lib as lgxlib
+
+from .fused import stream_of
+
+_X3_FIT = {}   # _x3_fits' answers
 
 
 def get_activation(name):
@@ -76,7 +84,6 @@ class _FusedMLP:
     ACT = {nn.ELU: 1, nn.Tanh: 2}
 
     def __init__(self, seq):
-        import os
         self.linears = [m for m in seq if isinstance(m, nn.Linear)]
         acts = {type(m) for m in seq if not isinstance(m, nn.Linear)}
         self.act = self.ACT.get(next(iter(acts)), 0) if len(acts) == 1 else 0
@@ -97,13 +104,10 @@ class _FusedMLP:
         with torch.no_grad():
             if self._ver.get("b") != ver or self._b is None or self._b[0].device != dev:
                 self._b = [l.bias.detach().contiguous() for l in self.linears]
-                self._bp = (C.c_void_p * n)(*[t.data_ptr() for t in self._b])
-                self._dims_c = (C.c_int32 * (n + 1))(*self.dims)
                 self._ver["b"] = ver
             if x3 and (self._ver.get("wl") != ver or self._wl is None or self._wl[0].device != dev):
-                from legged_gym_amd.sim import lib as lgxlib
                 lib = lgxlib.load()
-                stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+                stream = stream_of(self.linears[0].weight)
                 if self._wl is None or self._wl[0].device != dev:
                     self._wl = [torch.empty(int(lib.lgx_mlp_x3_weight_elems(l.out_features, l.in_features)),
                                             dtype=torch.int16, device=dev) for l in self.linears]
@@ -116,29 +120,18 @@ class _FusedMLP:
                 self._ver["wl"] = ver
             if not x3 and (self._ver.get("wt") != ver or self._wt is None or self._wt[0].device != dev):
                 self._wt = [l.weight.detach().t().contiguous() for l in self.linears]
-                self._wp = (C.c_void_p * n)(*[t.data_ptr() for t in self._wt])
                 self._ver["wt"] = ver
 
     def desc(self, x, y, x3=None):
-        from legged_gym_amd.sim import abi
         x3 = self.x3 if x3 is None else x3
         self._refresh(x3)
         self.last_x3 = x3
-        if x3:
-            d = abi.LgxMlpX3Desc()
-            d.x, d.y, d.rows, d.nl, d.act = x.data_ptr(), y.data_ptr(), x.shape[0], len(self.linears), self.act
-            for i, v in enumerate(self.dims):
-                d.dims[i] = v
-            for i in range(len(self.linears)):
-                d.weights[i] = self._wl[i].data_ptr()
-                d.biases[i] = self._b[i].data_ptr()
-            return d
-        d = abi.LgxMlpDesc()
+        d = abi.LgxMlpX3Desc() if x3 else abi.LgxMlpDesc()
         d.x, d.y, d.rows, d.nl, d.act = x.data_ptr(), y.data_ptr(), x.shape[0], len(self.linears), self.act
         for i, v in enumerate(self.dims):
             d.dims[i] = v
-        for i in range(len(self.linears)):
-            d.weights[i] = self._wt[i].data_ptr()
+        for i, w in enumerate(self._wl if x3 else self._wt):   # (each kernel's own weight image)
+            d.weights[i] = w.data_ptr()
             d.biases[i] = self._b[i].data_ptr()
         return d
 
@@ -152,20 +145,13 @@ class _FusedMLP:
 def launch_forward(descs, count, stream):
     """`count` (1 or 2) MLP descriptors in one lgx_mlp_forward_batch / lgx_mlp_x3_forward launch
     on `stream` (by descriptor type)."""
-    from legged_gym_amd.sim import abi
-    from legged_gym_amd.sim import lib as lgxlib
-    lib = lgxlib.load()
-    if isinstance(descs[0], abi.LgxMlpX3Desc):
-        lgxlib.check(lib.lgx_mlp_x3_forward(descs, count, stream), "lgx_mlp_x3_forward")
-    else:
-        lgxlib.check(lib.lgx_mlp_forward_batch(descs, count, stream), "lgx_mlp_forward_batch")
+    entry = "lgx_mlp_x3_forward" if isinstance(descs[0], abi.LgxMlpX3Desc) else "lgx_mlp_forward_batch"
+    lgxlib.check(getattr(lgxlib.load(), entry)(descs, count, stream), entry)
 
 
 def _x3_fits(mlps):
     """One lgx_mlp_x3_forward launch holds these networks' activations in LDS (decided once per
     combination, from dims alone)."""
-    from legged_gym_amd.sim import abi
-    from legged_gym_amd.sim import lib as lgxlib
     key = tuple(tuple(m.dims) for m in mlps) + tuple(m.act for m in mlps)
     fit = _X3_FIT.get(key)
     if fit is None:
@@ -178,15 +164,11 @@ def _x3_fits(mlps):
     return fit
 
 
-_X3_FIT = {}
-
-
 def make_descs(triples):
     """Descriptor array of one fused launch over up to two (fused_mlp, input, output) triples:
     split-bf16 (lgx_mlp_x3_forward) when every network takes it and their activations fit the LDS
     together, else f32 MFMA (lgx_mlp_forward_batch) for all of them.  Decided per launch: a pair
     that does not fit together leaves each network's own (single-network) launches on split-bf16."""
-    from legged_gym_amd.sim import abi
     mlps = [m for m, _, _ in triples]
     x3 = all(m.x3 for m in mlps) and _x3_fits(mlps)
     descs = ((abi.LgxMlpX3Desc if x3 else abi.LgxMlpDesc) * len(triples))()
@@ -201,8 +183,7 @@ def run_fused(pairs):
     for m, x in pairs:
         x = x.contiguous()
         triples.append((m, x, torch.empty(x.shape[0], m.dims[-1], device=x.device, dtype=torch.float)))
-    launch_forward(make_descs(triples), len(triples),
-                   C.c_void_p(torch.cuda.current_stream(pairs[0][1].device).cuda_stream))
+    launch_forward(make_descs(triples), len(triples), stream_of(pairs[0][1]))
     return [y for _, _, y in triples]
 
 
@@ -224,6 +205,7 @@ class ActorCritic(nn.Module):
         Normal.set_default_validate_args(False)
         self._fused_actor = _FusedMLP(self.actor)
         self._fused_critic = _FusedMLP(self.critic)
+        self.heads_fused = self._fused_actor.ok and self._fused_critic.ok   # one fused launch takes both heads
         self.use_fused_inference = True
 
     @staticmethod
@@ -277,21 +259,24 @@ class ActorCritic(nn.Module):
     def act_inference(self, observations):
         return self._actor_mean(observations)
 
-    def act_and_evaluate(self, observations, critic_observations):
-        """Rollout fast path: actor mean + critic value in ONE fused MFMA launch, then sample."""
-        if self._fused_ok(observations, self._fused_actor) and self._fused_critic.ok:
-            mean, value = run_fused([(self._fused_actor, observations), (self._fused_critic, critic_observations)])
-            self.distribution = Normal(mean, mean * 0.0 + self.std)
-            return self.distribution.sample(), value
-        return self.act(observations), self.evaluate(critic_observations)
+    def fused_heads(self, x):
+        """(actor, critic) fused MLPs when one fused launch takes both heads for the actor input `x` now, else None."""
+        ok = self.heads_fused and self._fused_ok(x, self._fused_actor)
+        return (self._fused_actor, self._fused_critic) if ok else None
 
     def rollout_forward(self, observations, critic_observations):
-        """(actor mean, critic value) in one fused MFMA launch, or None when the fused kernel does
-        not apply (CPU, non-ELU/tanh stacks, widths > 512)."""
-        if self._fused_ok(observations, self._fused_actor) and self._fused_critic.ok:
-            mean, value = run_fused([(self._fused_actor, observations), (self._fused_critic, critic_observations)])
-            return mean, value
-        return None
+        """(actor mean, critic value) of the two heads' inputs in one fused MFMA launch, or None when
+        the fused kernel does not apply (CPU, autograd, non-ELU/tanh stacks, widths > 512)."""
+        heads = self.fused_heads(observations)
+        return None if heads is None else tuple(run_fused(list(zip(heads, (observations, critic_observations)))))
+
+    def act_and_evaluate(self, observations, critic_observations):
+        """Rollout fast path: actor mean + critic value in ONE fused MFMA launch, then sample."""
+        out = self.rollout_forward(observations, critic_observations)
+        if out is None:
+            return ActorCritic.act(self, observations), ActorCritic.evaluate(self, critic_observations)
+        self.distribution = Normal(out[0], out[0] * 0.0 + self.std)
+        return self.distribution.sample(), out[1]
 
     def evaluate(self, critic_observations, **kwargs):
         if self._fused_ok(critic_observations, self._fused_critic):
@@ -390,16 +375,8 @@ class ActorCriticRecurrent(ActorCritic):
 
     def act_and_evaluate(self, observations, critic_observations):
         """act + evaluate (both memories advance one step); the two MLP heads in one fused launch."""
-        input_a = self.memory_a(observations).squeeze(0)
-        input_c = self.memory_c(critic_observations).squeeze(0)
-        if self._fused_ok(input_a, self._fused_actor) and self._fused_critic.ok:
-            mean, value = run_fused([(self._fused_actor, input_a), (self._fused_critic, input_c)])
-            self.distribution = Normal(mean, mean * 0.0 + self.std)
-            return self.distribution.sample(), value
-        return ActorCritic.act(self, input_a), ActorCritic.evaluate(self, input_c)
-
-    # the fused rollout path of PPO._act_fused feeds observations straight into the actor MLP
-    rollout_forward = None
+        return ActorCritic.act_and_evaluate(self, self.memory_a(observations).squeeze(0),
+                                            self.memory_c(critic_observations).squeeze(0))
 
     def get_hidden_states(self):
         return self.memory_a.hidden_states, self.memory_c.hidden_states

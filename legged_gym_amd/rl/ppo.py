@@ -10,16 +10,13 @@ global mean, so every rank applies the identical Adam step and N ranks x B envs 
 """
 import ctypes as C
 
-import os
-
 import torch
 import torch.nn as nn
 import torch.optim as optim
 
-from legged_gym_amd.sim import abi
-
-from .actor_critic import ActorCritic, launch_forward, make_descs
+from .actor_critic import ActorCritic
 from .fused_ppo import FusedPPOUpdate
+from .fused_rollout import FusedRollout
 from .storage import RolloutStorage
 
 
@@ -82,14 +79,15 @@ class PPO:
         self.max_grad_norm = max_grad_norm
         self.use_clipped_value_loss = use_clipped_value_loss
         self.dist = _dist()
-        self._fused = None
+        self._fused = self._rollout = self._deferred = None
         # process_env_step leaves its storage-row launch to the next act (one launch per step);
         # set by OnPolicyRunner, whose loop always calls act between env.step calls
         self.defer_store = False
-        self._pending_store = None
         if fused and use_fused_update and FusedPPOUpdate.supported(self.actor_critic):
             self._fused = FusedPPOUpdate(self)       # parameters become views of its flat buffer
             self.optimizer = self._fused.optimizer
+            if FusedRollout.supported(self.actor_critic):
+                self._rollout = FusedRollout(self, self._fused.lib)
         if self.dist is not None:
             self._broadcast_params()
 
@@ -140,91 +138,12 @@ class PPO:
                 self.dist.broadcast(p.data, src=0)
 
     # ---------------------------------------------------------------- rollout
-    def _rollout_kernels_ok(self, obs):
-        ac = self.actor_critic
-        return (self._fused is not None and obs.is_cuda and self.storage is not None
-                and getattr(ac, "rollout_forward", None) is not None and not ac.is_recurrent
-                and self.storage.step < self.storage.num_transitions_per_env)
-
-    def _act_fused(self, obs, critic_obs):
-        """act() + add_transitions' row writes (+ the deferred process_env_step store of the previous
-        step) in ONE launch: lgx_mlp_x3_forward_act runs the actor and critic MLPs and lgx_ppo_act's
-        arithmetic in the actor's last-layer epilogue (the critic writes its storage row directly).
-        LGX_FUSED_ACT=0, or a network pair the fused launch does not take: the MLP launch, then
-        lgx_ppo_act(_store) - bit-identical rows either way."""
-        ac = self.actor_critic
-        if not (ac._fused_ok(obs, ac._fused_actor) and ac._fused_critic.ok):
-            return None
-        st, s = self.storage, self.storage.step
-        main = torch.cuda.current_stream(obs.device)
-        obs = obs.contiguous()
-        critic_obs = critic_obs.contiguous()
-        A = ac._fused_actor.dims[-1]
-        if getattr(self, "_mean_buf", None) is None or self._mean_buf.shape != (obs.shape[0], A):
-            self._mean_buf = torch.empty(obs.shape[0], A, device=obs.device)
-        mean = self._mean_buf
-        descs = make_descs([(ac._fused_actor, obs, mean), (ac._fused_critic, critic_obs, st.values[s])])
-        if getattr(self, "_act_out", None) is None or self._act_out.shape != mean.shape:
-            self._act_out = torch.empty_like(mean)
-        # Normal.sample's standard-normal draws from torch's generator.  Default: one [N, A] draw
-        # per step, the RNG consumption of rsl_rl's Normal.sample (torch.normal(mu, std) =
-        # normal_(0, 1) * std + mu), so seeded runs draw the same noise as upstream.
-        # LGX_BATCHED_NOISE=1: one [T, N, A] draw per rollout (one launch instead of T; same
-        # distribution, different RNG stream, T*N*A floats kept)
-        T = st.num_transitions_per_env
-        if os.environ.get("LGX_BATCHED_NOISE", "0") == "1":
-            if s == 0 or getattr(self, "_noise", None) is None or self._noise.shape != (T,) + tuple(mean.shape):
-                self._noise = torch.randn((T,) + tuple(mean.shape), device=mean.device)
-            noise = self._noise[s]
-        else:
-            noise = torch.randn(mean.shape, device=mean.device)
-            self._noise = noise   # keep it alive until the act kernel has read it
-        a = abi.LgxPpoActArgs()
-        a.num_envs, a.num_actions, a.num_obs = mean.shape[0], mean.shape[1], obs.shape[1]
-        a.mu, a.value, a.std, a.noise = mean.data_ptr(), None, self.actor_critic.std.data_ptr(), noise.data_ptr()
-        a.obs = obs.data_ptr()
-        if st.privileged_observations is not None:
-            a.num_cobs, a.cobs, a.st_cobs = critic_obs.shape[1], critic_obs.data_ptr(), \
-                st.privileged_observations[s].data_ptr()
-        a.actions_out = self._act_out.data_ptr()
-        a.st_obs, a.st_actions, a.st_values = st.observations[s].data_ptr(), st.actions[s].data_ptr(), \
-            st.values[s].data_ptr()
-        a.st_logp, a.st_mu, a.st_sigma = st.actions_log_prob[s].data_ptr(), st.mu[s].data_ptr(), st.sigma[s].data_ptr()
-        lib = self._fused.lib
-        stream = C.c_void_p(main.cuda_stream)
-        pend = getattr(self, "_pending_store", None)
-        prev = pend[0] if pend is not None and pend[0].num_envs == a.num_envs else None
-        if prev is None:
-            self.flush_store()
-        fused = (isinstance(descs[0], abi.LgxMlpX3Desc) and not getattr(self, "_fused_act_off", False)
-                 and os.environ.get("LGX_FUSED_ACT", "1") != "0")
-        if fused and lib.lgx_mlp_x3_forward_act(descs, 2, C.byref(a), C.byref(prev) if prev is not None else None,
-                                                stream) != 0:
-            # (validated before any launch) a pair the fused launch does not take, e.g. the act
-            # rows past the LDS: the two-launch form from now on
-            self._fused_act_off, fused = True, False
-        if not fused:
-            launch_forward(descs, 2, stream)   # actor and critic in one launch
-            if prev is not None:   # the previous step's store rides along
-                self._fused.check(lib.lgx_ppo_act_store(C.byref(a), C.byref(prev), stream), "lgx_ppo_act_store")
-            else:
-                self._fused.check(lib.lgx_ppo_act(C.byref(a), stream), "lgx_ppo_act")
-        self.last_act_fused = fused
-        if prev is not None:
-            self._pending_store = None
-        t = self.transition
-        t.actions, t.values = self._act_out, st.values[s]
-        t.actions_log_prob, t.action_mean, t.action_sigma = st.actions_log_prob[s], st.mu[s], st.sigma[s]
-        t.observations, t.critic_observations = obs, critic_obs
-        t.in_storage = True
-        return self._act_out
-
     def act(self, obs, critic_obs):
-        t = self.transition
-        if self._rollout_kernels_ok(obs):
-            actions = self._act_fused(obs, critic_obs)
+        if self._rollout is not None:   # actions, values and the storage rows from the kernels
+            actions = self._rollout.act(obs, critic_obs)
             if actions is not None:
                 return actions
+        t = self.transition
         self.flush_store()   # (a deferred store reads the env's buffers before the next env.step)
         if self.actor_critic.is_recurrent:   # the memories' state before this step (rsl_rl PPO.act)
             t.hidden_states = self.actor_critic.get_hidden_states()
@@ -243,48 +162,31 @@ class PPO:
 
     def process_env_step(self, rewards, dones, infos):
         t = self.transition
-        if getattr(t, "in_storage", False):     # row already written by lgx_ppo_act
-            st = self.storage
-            a = abi.LgxPpoStoreArgs()
-            a.num_envs, a.gamma = st.num_envs, self.gamma
-            rewards = rewards.contiguous()
-            dones = dones.contiguous()
-            a.rew, a.reset = rewards.data_ptr(), dones.data_ptr()
-            to = infos.get("time_outs") if isinstance(infos, dict) else None
-            if to is not None:
-                to = to.contiguous()
-                a.time_outs = to.data_ptr()
-            a.st_values, a.st_rew, a.st_dones = st.values[st.step].data_ptr(), st.rewards[st.step].data_ptr(), \
-                st.dones[st.step].data_ptr()
-            if self.defer_store:
-                # launched with the next act (lgx_ppo_act_store) or by flush_store(): the env's
-                # reward / reset / time-out buffers hold this step's values until the next env.step,
-                # which the runner issues only after that act
-                self.flush_store()
-                self._pending_store = (a, rewards, dones, to)
-            else:
-                self._fused.check(self._fused.lib.lgx_ppo_store(C.byref(a), C.c_void_p(
-                    torch.cuda.current_stream(rewards.device).cuda_stream)), "lgx_ppo_store")
-            st.step += 1
-            t.clear()
-            self.actor_critic.reset(dones)
-            return
-        t.rewards = rewards.clone()
-        t.dones = dones
-        if "time_outs" in infos:  # bootstrap on time-outs
-            t.rewards += self.gamma * torch.squeeze(t.values * infos["time_outs"].unsqueeze(1).to(self.device), 1)
-        self.storage.add_transitions(t)
+        if t.in_storage:     # the other rows already written by FusedRollout.act
+            self._rollout.store(rewards, dones, infos)
+            self.storage.step += 1
+        else:
+            t.rewards = rewards.clone()
+            t.dones = dones
+            if "time_outs" in infos:  # bootstrap on time-outs
+                t.rewards += self.gamma * torch.squeeze(t.values * infos["time_outs"].unsqueeze(1).to(self.device), 1)
+            self.storage.add_transitions(t)
         t.clear()
         self.actor_critic.reset(dones)
 
+    @property
+    def last_act_fused(self):   # the last kernel-driven act was the one fused launch (False before it, and on CPU)
+        return self._rollout is not None and self._rollout.last_fused
+
     def flush_store(self):
-        """Launch a deferred lgx_ppo_store (defer_store) on its own."""
-        pend = getattr(self, "_pending_store", None)
-        if pend is None:
-            return
-        self._pending_store = None
-        self._fused.check(self._fused.lib.lgx_ppo_store(C.byref(pend[0]), C.c_void_p(
-            torch.cuda.current_stream(pend[1].device).cuda_stream)), "lgx_ppo_store")
+        """Launch a deferred process_env_step store (defer_store) on its own."""
+        if self._rollout is not None:
+            self._rollout.flush()
+
+    def drop_store(self):
+        """Forget a deferred store without launching it (cleanup after an error)."""
+        if self._rollout is not None:
+            self._rollout.drop()
 
     def _gather_moments(self, parts):
         """Every rank's flat float64 (count, mean, M2) advantage summaries, concatenated in rank order
@@ -388,5 +290,5 @@ class PPO:
         or None when none is pending."""
         if self._fused is not None:
             return self._fused.resolve()
-        out, self._deferred = getattr(self, "_deferred", None), None
+        out, self._deferred = self._deferred, None
         return out

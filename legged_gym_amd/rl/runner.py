@@ -210,7 +210,7 @@ class OnPolicyRunner:
             except Exception:
                 if completed:
                     raise
-                self.alg._pending_store = None
+                self.alg.drop_store()
         self.current_learning_iteration += num_learning_iterations
         if self.log_dir is not None:
             self.save(os.path.join(self.log_dir, f"model_{self.current_learning_iteration}.pt"))

@@ -473,7 +473,7 @@ def test_fused_act_launch_refused_falls_back(gpu):
     class Refusing:   # the library with lgx_mlp_x3_forward_act refusing
         def __getattr__(self, name):
             return (lambda *args: -1) if name == "lgx_mlp_x3_forward_act" else getattr(lib, name)
-    b._fused.lib = Refusing()
+    b._rollout.lib = Refusing()
     for p in (a, b):
         p.storage.clear()
     g = torch.Generator(device="cuda:0").manual_seed(9)
@@ -484,7 +484,7 @@ def test_fused_act_launch_refused_falls_back(gpu):
         torch.manual_seed(4)
         xb = b.act(obs, obs).clone()
     torch.cuda.synchronize()
-    assert a.last_act_fused and not b.last_act_fused and b._fused_act_off
+    assert a.last_act_fused and not b.last_act_fused and b._rollout.fused_off
     assert torch.equal(xa, xb)
     for k in ("observations", "actions", "values", "actions_log_prob", "mu", "sigma"):
         assert torch.equal(getattr(a.storage, k)[0], getattr(b.storage, k)[0]), k

@@ -279,25 +279,27 @@ def test_runner_reports_the_original_error(tmp_path):
     env = make_env("go1_flat_bench", num_envs=4, device="cpu", backend="oracle")
     cfg = class_to_dict(Go1RoughCfgPPO())
     cfg["runner"]["num_steps_per_env"] = 2
+    from legged_gym_amd.rl.fused_rollout import FusedRollout
     runner = OnPolicyRunner(env, cfg, None, device="cpu")
+    runner.alg._rollout = rollout = FusedRollout(runner.alg, None)   # (on the CPU it only holds the row)
     calls = {"n": 0}
     orig = env.step
 
     def failing_step(actions):
         calls["n"] += 1
         if calls["n"] == 2:
-            runner.alg._pending_store = ("stale",)        # a deferred row whose flush will fail
+            rollout.pending = ("stale",)        # a deferred row whose flush will fail
             raise ValueError("env step failed")
         return orig(actions)
 
     def bad_flush():
-        if runner.alg._pending_store is not None:
+        if rollout.pending is not None:
             raise RuntimeError("cleanup failed")
     env.step = failing_step
     runner.alg.flush_store = bad_flush
     with pytest.raises(ValueError, match="env step failed"):
         runner.learn(1)
-    assert runner.alg._pending_store is None and runner.alg.defer_store is False
+    assert rollout.pending is None and runner.alg.defer_store is False
 
 
 def test_policy_export_is_plain_torchscript(tmp_path):
