@@ -1014,6 +1014,30 @@ int lgx_ppo_symmetry_augment(const lgx_symmetry_args* args, void* stream);
  * [1, LGX_MAX_PRIV_OBS], a perm entry outside [0, width) or a sign that is not +-1. */
 int lgx_ppo_symmetry_check_table(const int32_t* perm, const float* sign, int32_t width);
 
+/* Symmetry mirror loss (rsl_rl 2.x symmetry_cfg.use_mirror_loss) on the fused update:
+ * lgx_ppo_loss_bwd for a minibatch of args->rows / 2 real rows followed by their mirror images (row
+ * rows / 2 + r is the mirror of row r, as lgx_ppo_symmetry_augment and the update's row indices
+ * make them), with the term
+ *   coeff * L_sym,  L_sym = 1 / (rows / 2 * A) * sum_r sum_j (mu(o'_r)[j] - sign[j] mu(o_r)[perm[j]])^2
+ * added to the loss: its gradient enters only through the mirror rows' action mean (the target is
+ * detached), i.e. dW4a, the actor head's bias gradient and the actor's dZ3.  A workgroup takes 16
+ * real rows and their 16 mirrors (head_in is overwritten in place, so it must own both); buffer
+ * sizes and dynamic LDS are lgx_ppo_loss_bwd_layout's for the same rows.  ppo_rows == rows: the PPO
+ * terms run over all rows as in lgx_ppo_loss_bwd.  ppo_rows == rows / 2: over the real rows alone
+ * (means over rows / 2; the mirror rows' seven storage arrays are not read and their d value is 0).
+ * sym_partials[lgx_ppo_mirror_partials_floats(rows)] receives one unscaled sum of squares per
+ * workgroup; lgx_ppo_mirror_loss_reduce sums `count` of them in a fixed order: out[0] = scale * sum
+ * (scale 1 / (rows / 2 * A) per minibatch).  No float atomics anywhere: two runs give the same bits.
+ * act_perm / act_sign [A]: the action table, device pointers that the launch trusts
+ * (lgx_ppo_symmetry_check_table); coeff = mirror_loss_coeff.
+ * LGX_EINVAL (message in lgx_last_error, nothing launched) for what lgx_ppo_loss_bwd refuses
+ * (head_in == NULL among it), odd rows, ppo_rows not in {rows / 2, rows}, a null table or partials
+ * pointer, or a coeff that is not a finite number > 0. */
+int lgx_ppo_loss_bwd_mirror(const lgx_ppo_loss_args* args, const int32_t* act_perm, const float* act_sign, float coeff,
+                            int64_t ppo_rows, float* sym_partials, float* head_partials, void* stream);
+int64_t lgx_ppo_mirror_partials_floats(int64_t rows);
+int lgx_ppo_mirror_loss_reduce(const float* partials, int64_t count, float scale, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -446,189 +446,57 @@ __device__ __forceinline__ float lb_rowsum(float v) {   // sum over the LB_LPR l
   return v;
 }
 
+// MIRROR (lgx_ppo_loss_bwd_mirror, the symmetry mirror loss): the minibatch is rows / 2 real rows and
+// then their mirror images (row rows / 2 + r mirrors row r), and a workgroup stages LB_PAIRS real
+// rows [LB_PAIRS w, ..) as local rows [0, LB_PAIRS) with their mirrors as local rows [LB_PAIRS,
+// LB_ROWS): it owns both partners, because phase 3 overwrites head_in in place and another
+// workgroup's rows may be gone already.  Every phase reaches a row through the local -> global row
+// map (`live`, `grow`).  Phase 2 adds, on the mirror rows, d/dmu of
+//   coeff / (rows / 2 * A) * sum (mu(o')[j] - sign[j] mu(o)[perm[j]])^2
+// (the real row's mu - bias added - read from LDS behind a barrier: the target, no gradient through
+// it) before dMU and the head-bias partial are written, so phase 3 and the partial layouts are
+// those of the plain form; the sum of squares goes to sym_partials[workgroup] in row order.  Rows
+// >= ppo_rows take no part in the PPO terms (none of their storage arrays is read), which run over
+// ppo_rows rows; the KL / surrogate / value-loss partials are scaled by rows / ppo_rows (1 or 2,
+// exact), since the finalize divides them by rows.
+constexpr int LB_PAIRS = LB_ROWS / 2;
+struct ppo_mirror_args {   // what the mirror form takes beside lgx_ppo_loss_args (lgx_ppo_loss_bwd_mirror)
+  const int32_t* act_perm;   // [A] the action table
+  const float* act_sign;
+  float* sym_partials;       // [workgroups]
+  int64_t ppo_rows;          // rows or rows / 2
+  float coeff;
+};
+
 template <int MAXA>
 __global__ void __launch_bounds__(TPB)
 ppo_loss_bwd_kernel(lgx_ppo_loss_args a, float* __restrict__ hparts) {
-  constexpr int JQ = (MAXA + LB_LPR - 1) / LB_LPR;   // actions per lane
-  constexpr int DS = ((MAXA + 1 + 3) / 4) * 4;      // dMU row (+ dV), 16-byte LDS reads
-  const int A = a.num_actions, H = a.hidden, H4 = H >> 2, HS = H + 4;
-  const int NP = 2 * A + 4;
-  extern __shared__ float4 lb_dyn[];
-  float* ylds = reinterpret_cast<float*>(lb_dyn);            // [2][LB_ROWS][HS]
-  float* wlds = ylds + 2 * LB_ROWS * HS;                      // [A + 1][H]: W4a rows, then w4c
-  __shared__ __align__(16) float dmu[LB_ROWS][DS];
-  __shared__ float red[LB_ROWS][2 * MAXA + 4 + 1];
-  const int t = threadIdx.x;
-  const int64_t r0 = (int64_t)blockIdx.x * LB_ROWS;
-  const int nr = (int)min((int64_t)LB_ROWS, a.rows - r0);
-  float* A3 = const_cast<float*>(a.head_in);
-  // ---- stage the rows (rows past M as zeros) and the head weights
-  for (int i = t; i < 2 * LB_ROWS * H4; i += TPB) {
-    const int nrow = i / H4, c4 = i - nrow * H4;              // nrow = net * LB_ROWS + row
-    const int net = nrow >= LB_ROWS, rr = nrow - net * LB_ROWS;
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (rr < nr) v = reinterpret_cast<const float4*>(A3 + ((int64_t)net * a.rows + r0 + rr) * H)[c4];
-    *reinterpret_cast<float4*>(ylds + nrow * HS + 4 * c4) = v;
-  }
-  for (int i = t; i < (A + 1) * H4; i += TPB)
-    reinterpret_cast<float4*>(wlds)[i] = i < A * H4 ? reinterpret_cast<const float4*>(a.W4a)[i]
-                                                    : reinterpret_cast<const float4*>(a.W4c)[i - A * H4];
+  constexpr bool MIRROR = false;
+  const ppo_mirror_args ms{};
+#include "lgx_ppo_loss_bwd_body.h"
+}
+
+template <int MAXA>
+__global__ void __launch_bounds__(TPB)
+ppo_loss_bwd_mirror_kernel(lgx_ppo_loss_args a, float* __restrict__ hparts, ppo_mirror_args ms) {
+  constexpr bool MIRROR = true;
+#include "lgx_ppo_loss_bwd_body.h"
+}
+
+// sum of the mirror launch's symmetry partials -> out[0] = scale * sum (one workgroup, fixed order:
+// lane-strided chains, then the tree)
+__global__ void __launch_bounds__(TPB)
+mirror_loss_reduce_kernel(const float* __restrict__ parts, int64_t n, float scale, float* __restrict__ out) {
+  __shared__ float red[TPB];
+  float s = 0.f;
+  for (int64_t i = threadIdx.x; i < n; i += TPB) s += parts[i];
+  red[threadIdx.x] = s;
   __syncthreads();
-  // ---- 1. output layers
-  const int rr = t / LB_LPR, q = t % LB_LPR;
-  float hv[MAXA + 1];
-#pragma unroll
-  for (int j = 0; j <= MAXA; ++j) hv[j] = 0.f;
-  {
-    const float* ya = ylds + rr * HS;
-    const float* yc = ylds + (LB_ROWS + rr) * HS;
-    const float4* w4 = reinterpret_cast<const float4*>(wlds);
-    for (int c4 = q; c4 < H4; c4 += LB_LPR) {
-      const float4 x = *reinterpret_cast<const float4*>(ya + 4 * c4);
-      const float4 y = *reinterpret_cast<const float4*>(yc + 4 * c4);
-#pragma unroll
-      for (int j = 0; j < MAXA; ++j)
-        if (j < A) {
-          const float4 w = w4[j * H4 + c4];
-          hv[j] += x.x * w.x + x.y * w.y + x.z * w.z + x.w * w.w;
-        }
-      const float4 w = w4[A * H4 + c4];
-      hv[MAXA] += y.x * w.x + y.y * w.y + y.z * w.z + y.w * w.w;
-    }
+  for (int w = TPB / 2; w > 0; w >>= 1) {
+    if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+    __syncthreads();
   }
-#pragma unroll
-  for (int j = 0; j <= MAXA; ++j) hv[j] = lb_rowsum(hv[j]);
-  // ---- 2. loss per row (lane q: actions q + LB_LPR m)
-  float* my = red[rr];
-  const bool valid = rr < nr;
-  {
-    const int64_t r = r0 + rr;
-    const int64_t g = valid ? (a.idx ? a.idx[r] : r) : 0;
-    const float invM = 1.0f / (float)a.rows;
-    const float half_log_2pi = 0.91893853320467274178f;
-    float mu[JQ], sd[JQ], act[JQ];
-    float logp = 0.f, kl = 0.f;
-#pragma unroll
-    for (int m = 0; m < JQ; ++m) {
-      const int j = q + LB_LPR * m;
-      float h = 0.f;
-#pragma unroll
-      for (int jj = 0; jj < MAXA; ++jj) h = jj == j ? hv[jj] : h;
-      mu[m] = sd[m] = 1.f;
-      act[m] = 0.f;
-      if (valid && j < A) {
-        mu[m] = h + a.b4a[j];
-        sd[m] = a.std[j];
-        act[m] = a.actions[g * A + j];
-        const float var = sd[m] * sd[m];
-        const float d = act[m] - mu[m];
-        logp += -(d * d) / (2.f * var) - logf(sd[m]) - half_log_2pi;
-        const float so = a.old_sigma[g * A + j], mo = a.old_mu[g * A + j];
-        kl += logf(sd[m] / so + 1.e-5f) + (so * so + (mo - mu[m]) * (mo - mu[m])) / (2.f * var) - 0.5f;
-      }
-    }
-    logp = lb_rowsum(logp);
-    kl = lb_rowsum(kl);
-    float dlogp = 0.f, surr = 0.f, vl = 0.f, dv = 0.f;
-    if (valid) {
-      const float adv = a.advantages[g];
-      const float ratio = expf(logp - a.old_logp[g]);
-      const float lo = 1.f - a.clip_param, hi = 1.f + a.clip_param;
-      const float rc = fminf(fmaxf(ratio, lo), hi);
-      const float s1 = -adv * ratio, s2 = -adv * rc;
-      const bool inside = ratio >= lo && ratio <= hi;
-      float dsdr;   // torch.maximum backward: ties split the gradient; clamp passes it inside [lo, hi]
-      if (s1 > s2) dsdr = -adv;
-      else if (s1 < s2) dsdr = inside ? -adv : 0.f;
-      else dsdr = 0.5f * (-adv) + 0.5f * (inside ? -adv : 0.f);
-      surr = fmaxf(s1, s2);
-      dlogp = dsdr * invM * ratio;
-      const float v = hv[MAXA] + a.b4c[0];
-      const float tv = a.target_values[g], ret = a.returns[g];
-      if (a.use_clipped_value_loss) {
-        const float dvt = v - tv;
-        const float vc = tv + fminf(fmaxf(dvt, -a.clip_param), a.clip_param);
-        const bool vin = dvt >= -a.clip_param && dvt <= a.clip_param;
-        const float u1 = (v - ret) * (v - ret), u2 = (vc - ret) * (vc - ret);
-        vl = fmaxf(u1, u2);
-        const float g1 = 2.f * (v - ret), g2 = vin ? 2.f * (vc - ret) : 0.f;
-        dv = u1 > u2 ? g1 : (u1 < u2 ? g2 : 0.5f * g1 + 0.5f * g2);
-      } else {
-        vl = (ret - v) * (ret - v);
-        dv = 2.f * (v - ret);
-      }
-      dv *= a.value_loss_coef * invM;
-    }
-#pragma unroll
-    for (int m = 0; m < JQ; ++m) {
-      const int j = q + LB_LPR * m;
-      if (j < A) {
-        const float var = sd[m] * sd[m];
-        const float d = act[m] - mu[m];
-        const float dm = valid ? dlogp * d / var : 0.f;
-        dmu[rr][j] = dm;
-        my[A + j] = dm;
-        my[j] = valid ? dlogp * (d * d / (var * sd[m]) - 1.f / sd[m]) : 0.f;
-      }
-    }
-    if (q == 0) {
-      dmu[rr][A] = dv;
-      my[2 * A] = dv;
-      my[2 * A + 1] = valid ? kl : 0.f;
-      my[2 * A + 2] = surr;
-      my[2 * A + 3] = vl;
-    }
-  }
-  __syncthreads();
-  if (t < NP) {   // loss partials of this workgroup (rows in order)
-    float s = 0.f;
-    for (int i = 0; i < LB_ROWS; ++i) s += red[i][t];
-    a.partials[(int64_t)blockIdx.x * NP + t] = s;
-  }
-  // ---- 3. output-layer backward (as head_bwd_kernel; A3 rows from LDS)
-  float* P = hparts + (int64_t)blockIdx.x * ((A + 1) * H + 2 * H);
-  for (int o = t; o < 2 * H; o += TPB) {
-    const int net = o >= H, c = o - net * H;
-    const int nj = net == 0 ? A : 1;
-    float w[MAXA], acc[MAXA];
-#pragma unroll
-    for (int j = 0; j < MAXA; ++j) {
-      w[j] = j < nj ? wlds[(net == 0 ? j : A) * H + c] : 0.f;
-      acc[j] = 0.f;
-    }
-    const float* ycol = ylds + net * LB_ROWS * HS + c;
-    float* col = A3 + ((int64_t)net * a.rows + r0) * H + c;
-    float cs = 0.f;
-    for (int i = 0; i < nr; ++i) {
-      const float y = ycol[i * HS];
-      float drow[DS];
-#pragma unroll
-      for (int u = 0; u < DS / 4; ++u) {
-        const float4 v = *reinterpret_cast<const float4*>(&dmu[i][4 * u]);
-        drow[4 * u] = v.x; drow[4 * u + 1] = v.y; drow[4 * u + 2] = v.z; drow[4 * u + 3] = v.w;
-      }
-      float dA = 0.f;
-      if (net == 0) {
-#pragma unroll
-        for (int j = 0; j < MAXA; ++j)
-          if (j < nj) { acc[j] += drow[j] * y; dA += drow[j] * w[j]; }
-      } else {
-        float d = 0.f;
-#pragma unroll
-        for (int j = 0; j <= MAXA; ++j) d = (j == A) ? drow[j] : d;   // dV column
-        acc[0] += d * y;
-        dA = d * w[0];
-      }
-      const float dz = dA * elu_grad_from_out(y);
-      col[(int64_t)i * H] = dz;
-      cs += dz;
-    }
-    const int jo = net == 0 ? 0 : A;
-#pragma unroll
-    for (int j = 0; j < MAXA; ++j)
-      if (j < nj) P[(jo + j) * H + c] = acc[j];
-    P[(A + 1) * H + o] = cs;
-  }
+  if (threadIdx.x == 0) out[0] = red[0] * scale;
 }
 
 // ---------------------------------------------------------------------------------------- elu bwd
@@ -1051,40 +919,87 @@ extern "C" int lgx_ppo_loss_bwd_layout(int64_t rows, int32_t num_actions, int32_
   return LGX_OK;
 }
 
-extern "C" int lgx_ppo_loss_bwd(const lgx_ppo_loss_args* args, float* head_partials, void* stream) {
-  if (!args) return lgx_fail(LGX_EINVAL, "lgx_ppo_loss_bwd: null args");
+// lgx_ppo_loss_bwd (ms == nullptr) and lgx_ppo_loss_bwd_mirror: the checks they share and the launch
+static int loss_bwd_launch(const lgx_ppo_loss_args* args, const ppo_mirror_args* ms, float* head_partials,
+                           void* stream) {
+  if (!args) return lgx_fail(LGX_EINVAL, ms ? "lgx_ppo_loss_bwd_mirror: null args" : "lgx_ppo_loss_bwd: null args");
   const lgx_ppo_loss_args& a = *args;
   if (a.rows <= 0 || a.num_actions <= 0 || a.num_actions > LGX_PPO_MAX_ACTIONS || !a.b4a || !a.b4c || !a.std ||
       !a.actions || !a.old_logp || !a.old_mu || !a.old_sigma || !a.advantages || !a.target_values || !a.returns ||
       !a.partials || !a.g_std || !a.g_b4a || !a.g_b4c || !a.stats || !head_partials)
-    return lgx_fail(LGX_EINVAL, "lgx_ppo_loss_bwd: bad args");
+    return lgx_fail(LGX_EINVAL, ms ? "lgx_ppo_loss_bwd_mirror: bad args" : "lgx_ppo_loss_bwd: bad args");
   if (!a.head_in || !a.W4a || !a.W4c || a.hidden <= 0 || a.hidden % 16)
-    return lgx_fail(LGX_EINVAL, "lgx_ppo_loss_bwd: head_in / W4a / W4c required, hidden % 16 == 0");
+    return lgx_fail(LGX_EINVAL, ms ? "lgx_ppo_loss_bwd_mirror: head_in / W4a / W4c required, hidden % 16 == 0"
+                                   : "lgx_ppo_loss_bwd: head_in / W4a / W4c required, hidden % 16 == 0");
+  if (ms) {
+    if (a.rows % 2) return lgx_fail(LGX_EINVAL, "lgx_ppo_loss_bwd_mirror: rows must be even (real rows, then their mirrors)");
+    if (ms->ppo_rows != a.rows && ms->ppo_rows != a.rows / 2)
+      return lgx_fail(LGX_EINVAL, "lgx_ppo_loss_bwd_mirror: ppo_rows must be rows or rows / 2");
+    if (!ms->act_perm || !ms->act_sign || !ms->sym_partials)
+      return lgx_fail(LGX_EINVAL, "lgx_ppo_loss_bwd_mirror: null action table or symmetry partials");
+    if (!(ms->coeff > 0.f) || !std::isfinite(ms->coeff))
+      return lgx_fail(LGX_EINVAL, "lgx_ppo_loss_bwd_mirror: coeff must be a finite number > 0");
+  }
   int64_t lay[3];
   lgx_ppo_loss_bwd_layout(a.rows, a.num_actions, a.hidden, lay);
-  if (lay[2] > 96 * 1024) return lgx_fail(LGX_EINVAL, "lgx_ppo_loss_bwd: hidden too wide for the LDS row stage");
+  if (lay[2] > 96 * 1024)
+    return lgx_fail(LGX_EINVAL, ms ? "lgx_ppo_loss_bwd_mirror: hidden too wide for the LDS row stage"
+                                   : "lgx_ppo_loss_bwd: hidden too wide for the LDS row stage");
   static const bool attr_ok =
-      lgx_allow_dynamic_lds({&ppo_loss_bwd_kernel<12>, &ppo_loss_bwd_kernel<LGX_PPO_MAX_ACTIONS>}, 96 * 1024);
+      lgx_allow_dynamic_lds({&ppo_loss_bwd_kernel<12>, &ppo_loss_bwd_kernel<LGX_PPO_MAX_ACTIONS>}, 96 * 1024) &&
+      lgx_allow_dynamic_lds({&ppo_loss_bwd_mirror_kernel<12>, &ppo_loss_bwd_mirror_kernel<LGX_PPO_MAX_ACTIONS>},
+                            96 * 1024);
   if (!attr_ok) return lgx_fail(LGX_EHIP, "lgx_ppo_loss_bwd: hipFuncSetAttribute failed");
+  // (mirror: LB_PAIRS pairs per workgroup over rows / 2 pairs - the same count, rows being even)
   const int blocks = (int)((a.rows + LB_ROWS - 1) / LB_ROWS);
+  const dim3 grid(blocks), block(TPB);
+  const size_t lds = (size_t)lay[2];
+  const bool small = a.num_actions <= 12;
   // (LGX_LAUNCH on the call's last launch: a bound event, lgx_launch_bind_event, marks its end)
-  if (a.defer_finalize) {
-    if (a.num_actions <= 12)
-      LGX_LAUNCH(ppo_loss_bwd_kernel<12>, dim3(blocks), dim3(TPB), (size_t)lay[2], LGX_STREAM(stream), a,
-                 head_partials);
-    else
-      LGX_LAUNCH(ppo_loss_bwd_kernel<LGX_PPO_MAX_ACTIONS>, dim3(blocks), dim3(TPB), (size_t)lay[2],
-                 LGX_STREAM(stream), a, head_partials);
+  if (ms && a.defer_finalize) {
+    if (small) LGX_LAUNCH(ppo_loss_bwd_mirror_kernel<12>, grid, block, lds, LGX_STREAM(stream), a, head_partials, *ms);
+    else LGX_LAUNCH(ppo_loss_bwd_mirror_kernel<LGX_PPO_MAX_ACTIONS>, grid, block, lds, LGX_STREAM(stream), a,
+                    head_partials, *ms);
+  } else if (ms) {
+    if (small) hipLaunchKernelGGL(ppo_loss_bwd_mirror_kernel<12>, grid, block, lds, LGX_STREAM(stream), a,
+                                  head_partials, *ms);
+    else hipLaunchKernelGGL(ppo_loss_bwd_mirror_kernel<LGX_PPO_MAX_ACTIONS>, grid, block, lds, LGX_STREAM(stream), a,
+                            head_partials, *ms);
+  } else if (a.defer_finalize) {
+    if (small) LGX_LAUNCH(ppo_loss_bwd_kernel<12>, grid, block, lds, LGX_STREAM(stream), a, head_partials);
+    else LGX_LAUNCH(ppo_loss_bwd_kernel<LGX_PPO_MAX_ACTIONS>, grid, block, lds, LGX_STREAM(stream), a, head_partials);
   } else {
-    if (a.num_actions <= 12)
-      hipLaunchKernelGGL(ppo_loss_bwd_kernel<12>, dim3(blocks), dim3(TPB), (size_t)lay[2], LGX_STREAM(stream), a,
-                         head_partials);
-    else
-      hipLaunchKernelGGL(ppo_loss_bwd_kernel<LGX_PPO_MAX_ACTIONS>, dim3(blocks), dim3(TPB), (size_t)lay[2],
-                         LGX_STREAM(stream), a, head_partials);
-    LGX_LAUNCH(ppo_loss_finalize_kernel, dim3(1), dim3(TPB), 0, LGX_STREAM(stream), a, blocks);
+    if (small) hipLaunchKernelGGL(ppo_loss_bwd_kernel<12>, grid, block, lds, LGX_STREAM(stream), a, head_partials);
+    else hipLaunchKernelGGL(ppo_loss_bwd_kernel<LGX_PPO_MAX_ACTIONS>, grid, block, lds, LGX_STREAM(stream), a,
+                            head_partials);
   }
-  return lgx_hip_status("lgx_ppo_loss_bwd");
+  if (!a.defer_finalize)
+    LGX_LAUNCH(ppo_loss_finalize_kernel, dim3(1), dim3(TPB), 0, LGX_STREAM(stream), a, blocks);
+  return lgx_hip_status(ms ? "lgx_ppo_loss_bwd_mirror" : "lgx_ppo_loss_bwd");
+}
+
+extern "C" int lgx_ppo_loss_bwd(const lgx_ppo_loss_args* args, float* head_partials, void* stream) {
+  return loss_bwd_launch(args, nullptr, head_partials, stream);
+}
+
+extern "C" int lgx_ppo_loss_bwd_mirror(const lgx_ppo_loss_args* args, const int32_t* act_perm, const float* act_sign,
+                                       float coeff, int64_t ppo_rows, float* sym_partials, float* head_partials,
+                                       void* stream) {
+  const ppo_mirror_args ms{act_perm, act_sign, sym_partials, ppo_rows, coeff};
+  return loss_bwd_launch(args, &ms, head_partials, stream);
+}
+
+extern "C" int64_t lgx_ppo_mirror_partials_floats(int64_t rows) {
+  return (rows / 2 + LB_PAIRS - 1) / LB_PAIRS;
+}
+
+extern "C" int lgx_ppo_mirror_loss_reduce(const float* partials, int64_t count, float scale, float* out,
+                                          void* stream) {
+  if (!partials || !out || count <= 0 || !std::isfinite(scale))
+    return lgx_fail(LGX_EINVAL, "lgx_ppo_mirror_loss_reduce: bad args");
+  hipLaunchKernelGGL(mirror_loss_reduce_kernel, dim3(1), dim3(TPB), 0, LGX_STREAM(stream), partials, count, scale,
+                     out);
+  return lgx_hip_status("lgx_ppo_mirror_loss_reduce");
 }
 
 extern "C" int64_t lgx_colsum_partials_floats(int64_t rows, int32_t hidden, int32_t nets) {

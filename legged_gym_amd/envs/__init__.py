@@ -6,7 +6,8 @@ with runner.empirical_normalization: running mean / std in front of actor and cr
 an observation history: cfg.history), go1_rough_actrand (go1_rough with per-env drive gains and
 action latency: cfg.actuator_rand), go1_rough_cmdcur (go1_rough with the command curriculum:
 commands.curriculum, lin_vel_x widening from half of go1_rough's range), go1_rough_sym (go1_rough
-trained with left-right symmetry data augmentation: algorithm.symmetry), go1_flat_bench (C2 as
+trained with left-right symmetry data augmentation: algorithm.symmetry), go1_rough_mirror (go1_rough
+trained with the symmetry mirror loss: algorithm.symmetry.use_mirror_loss), go1_flat_bench (C2 as
 BASELINE states it: PD, no domain randomisation), anymal_c_rough (C5), anymal_c_flat, and the
 remaining robots of the reference registry: anymal_b, a1, a1_src, aliengo and cassie (the biped:
 2 legs x 6 joints on the dense physics kernel).
@@ -26,8 +27,8 @@ from .cassie.cassie_config import CassieRoughCfg, CassieRoughCfgPPO
 from .base.legged_robot_config import LeggedRobotCfg, LeggedRobotCfgPPO
 from .go1.go1 import Go1
 from .go1.go1_config import (Go1FlatBenchCfg, Go1RoughActRandCfg, Go1RoughAsymCfg, Go1RoughCfg, Go1RoughCfgPPO,
-                             Go1RoughCmdCurCfg, Go1RoughHistCfg, Go1RoughNormCfgPPO, Go1RoughSymCfgPPO,
-                             Go1RoughTerrainCfg)
+                             Go1RoughCmdCurCfg, Go1RoughHistCfg, Go1RoughMirrorCfgPPO, Go1RoughNormCfgPPO,
+                             Go1RoughSymCfgPPO, Go1RoughSymMirrorCfgPPO, Go1RoughTerrainCfg)
 
 task_registry.register("go1", Go1, Go1RoughCfg(), Go1RoughCfgPPO())
 task_registry.register("go1_flat_bench", Go1, Go1FlatBenchCfg(), Go1RoughCfgPPO())
@@ -48,3 +49,5 @@ task_registry.register_variant("go1_rough_asym_norm", "go1_rough_asym", Go1Rough
 task_registry.register_variant("go1_rough_cmdcur", "go1_rough", Go1RoughCfgPPO(), env_cfg=Go1RoughCmdCurCfg())
 # go1_rough trained on its rollout rows and their mirror images: the same env, another train cfg
 task_registry.register_variant("go1_rough_sym", "go1_rough", Go1RoughSymCfgPPO())
+# go1_rough trained with the mirror loss on the actor's equivariance defect: the same env, another train cfg
+task_registry.register_variant("go1_rough_mirror", "go1_rough", Go1RoughMirrorCfgPPO())

@@ -249,9 +249,18 @@ class LeggedRobotCfgPPO(BaseConfig):  # ref :218-255
             of minibatches unchanged); the tables come from the env (LeggedRobot.symmetry_tables(),
             envs/base/symmetry.py) and the mirror rows are written on the device once per update.
             Deviation from rsl_rl 2.x: the adaptive schedule's KL is the mean over all 2 M rows (mirror
-            rows carry the mirrored old mu / sigma), where rsl_rl 2.x averages the real half only.  Not
-            supported (ValueError): recurrent policies, runner.empirical_normalization together with
-            it, and any other key here (use_mirror_loss among them).  False: nothing changes."""
+            rows carry the mirrored old mu / sigma), where rsl_rl 2.x averages the real half only.
+            use_mirror_loss = True with mirror_loss_coeff = c (both set on the config classes that use
+            them, e.g. Go1RoughMirrorCfgPPO) adds c x mean((mu(mirror(o)) -
+            mirror(mu(o)).detach())^2) over the minibatch's M rows x A actions to the loss.  Alone, the
+            PPO terms and the KL run over the M rollout rows as without symmetry; the storage and the
+            forward / backward still cover 2 M rows, so the update costs what augmentation costs.  With
+            augmentation the term comes on top of the 2 M-row PPO loss.  Deviation: with
+            use_mirror_loss = False nothing is computed and mirror_loss_coeff is ignored (rsl_rl 2.x
+            logs a detached symmetry loss then).  Not supported (ValueError): use_mirror_loss without a
+            finite mirror_loss_coeff > 0, recurrent policies, runner.empirical_normalization together
+            with either flag, robots whose tables cannot be built, and any other key here.  Both flags
+            False: nothing changes."""
             use_data_augmentation = False
 
     class runner:

@@ -14,6 +14,9 @@ go1_rough_cmdcur.
 `Go1RoughSymCfgPPO` trains with left-right symmetry data augmentation: go1_rough under
 it is registered as go1_rough_sym; `Go1RoughAsymHistSymCfg` names the widest combination (history actor,
 privileged critic) meant to be trained with it (not registered).
+`Go1RoughMirrorCfgPPO` trains with the symmetry mirror loss alone: go1_rough under it is
+registered as go1_rough_mirror; `Go1RoughSymMirrorCfgPPO` pairs the mirror loss with the augmentation (not
+registered).
 """
 from legged_gym_amd.envs.base.legged_robot_config import LeggedRobotCfg, LeggedRobotCfgPPO
 
@@ -87,6 +90,29 @@ class Go1RoughSymCfgPPO(Go1RoughCfgPPO):
     class algorithm(Go1RoughCfgPPO.algorithm):
         class symmetry(Go1RoughCfgPPO.algorithm.symmetry):
             use_data_augmentation = True
+
+
+class Go1RoughMirrorCfgPPO(Go1RoughCfgPPO):
+    """Go1RoughCfgPPO with the symmetry mirror loss alone (rsl_rl 2.x symmetry_cfg.use_mirror_loss without
+    use_data_augmentation): the PPO terms run over the rollout rows as in go1_rough, and
+    mirror_loss_coeff x mean((mu(mirror(o)) - mirror(mu(o)))^2) penalises the actor's equivariance
+    defect on every minibatch.  The update costs what go1_rough_sym's does (the actor and the critic
+    run over the mirror rows too).  mirror_loss_coeff = 1.0 is untuned: no learning curve has been
+    produced with it."""
+    class algorithm(Go1RoughCfgPPO.algorithm):
+        class symmetry(Go1RoughCfgPPO.algorithm.symmetry):
+            use_mirror_loss = True
+            mirror_loss_coeff = 1.0
+
+
+class Go1RoughSymMirrorCfgPPO(Go1RoughCfgPPO):
+    """Go1RoughSymCfgPPO plus the mirror loss (both halves of rsl_rl 2.x symmetry_cfg): the PPO terms
+    over the rollout rows and their mirror images, the mirror term on top.  mirror_loss_coeff is
+    untuned, as in Go1RoughMirrorCfgPPO."""
+    class algorithm(Go1RoughCfgPPO.algorithm):
+        class symmetry(Go1RoughSymCfgPPO.algorithm.symmetry):
+            use_mirror_loss = True
+            mirror_loss_coeff = 1.0
 
 
 class Go1FlatBenchCfg(Go1RoughCfg):

@@ -10,6 +10,8 @@ Per minibatch (M rows), no host synchronisation (the stages of `_minibatch_body`
           value loss / entropy / KL, the analytic gradient w.r.t. mu, value, std, head biases and
           the output-layer backward; its finalize (in the reduction launch) applies the device-side
           adaptive schedule (data-parallel: lgx_ppo_adapt_lr after the all-reduce the KL rides in)
+          (symmetry.use_mirror_loss: lgx_ppo_loss_bwd_mirror in its place, the same launch with the
+          mirror term on the minibatch's mirror rows)
   backward: per layer lgx_gemm_tn for dW (split-K, on a second stream) next to lgx_gemm_nt for dA
           with the ELU' epilogue; the bias gradients are column sums from either
   reductions: lgx_reduce_slices*: all split-K and bias partials -> flat gradient
@@ -243,6 +245,8 @@ class FusedPPOUpdate:
     _t_events = _c_events = ()
     Xall = Xall2 = Xcall = None                  # _gather_all's buffers
     time_augment, augment_events = False, ()     # tools/train_time.py: event pairs around each augment launch
+    sym_parts = sym_stat = _pin_sym = None       # mirror loss: per-minibatch partials, the update's mean, its readback
+    _sym_slot = 0
     _rec_idx = _mem_ctx = None                   # recurrent minibatches
 
     @staticmethod
@@ -378,6 +382,13 @@ class FusedPPOUpdate:
         lay = (C.c_int64 * 3)()
         self.check(self.lib.lgx_ppo_loss_bwd_layout(M, A, H, lay), "loss_bwd_layout")
         self.loss_bwd = self.head_in_loss and lay[2] <= 96 * 1024 and sw.loss_bwd
+        if self.ppo.mirror_loss_coeff is not None and not self.loss_bwd:
+            # the mirror term lives in the paired form of that launch alone: never train without it
+            self.M = None
+            why = ("LGX_PPO_LOSS_BWD=0" if not sw.loss_bwd else "LGX_PPO_HEAD_IN_LOSS=0" if not sw.head_in_loss else
+                   f"a head of {A} actions on {H} hidden units does not fit lgx_ppo_loss_bwd's LDS")
+            raise ValueError("symmetry.use_mirror_loss needs the fused loss / output-layer launch "
+                             f"(lgx_ppo_loss_bwd_mirror), which this plan does not run: {why}")
         if self.loss_bwd:
             self.loss_parts = torch.empty(int(lay[0]), device=dev)
             self.head_parts = torch.empty(int(lay[1]), device=dev)
@@ -636,7 +647,8 @@ class FusedPPOUpdate:
         nmb = ppo.num_mini_batches
         B = ppo.storage.num_transitions_per_env * ppo.storage.num_envs
         M = B // nmb
-        # symmetry augmentation: M real rows + their M mirrors per minibatch through the same kernels
+        # symmetry augmentation / mirror loss: M real rows + their M mirrors per minibatch through the
+        # same kernels (the mirror loss alone: the PPO terms over the real rows, lgx_ppo_loss_bwd_mirror's ppo_rows)
         sym = ppo.storage.symmetry is not None
         Mr = 2 * M if sym else M
         stream = self._begin_update(Mr)
@@ -683,6 +695,7 @@ class FusedPPOUpdate:
             if ppo.desired_kl is not None and ppo.schedule == "adaptive":
                 self.optimizer.lr_dev.fill_(ppo.learning_rate)
             self.stats.zero_()
+        self._sym_slot = 0
         return C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
 
     def _storage_views(self):
@@ -732,12 +745,20 @@ class FusedPPOUpdate:
     def _finish(self, n, defer):
         """The update's readback (statistics, adapted learning rate) over its n minibatches: now, or
         deferred to pinned memory behind an event (resolve())."""
+        mirror = self.ppo.mirror_loss_coeff is not None
+        if mirror:
+            self._reduce_symmetry_loss(n)
         if not defer:
-            return self._apply_readback(self.stats.tolist(), float(self.optimizer.lr_dev.item()), n)
+            return self._apply_readback(self.stats.tolist(), float(self.optimizer.lr_dev.item()), n,
+                                        float(self.sym_stat.item()) if mirror else None)
         if self._pin_stats is None:
             self._pin_stats = torch.empty(self.stats.shape, dtype=self.stats.dtype).pin_memory()
             self._pin_lr = torch.empty(1, dtype=self.optimizer.lr_dev.dtype).pin_memory()
             self._pin_ev = torch.cuda.Event()
+        if mirror:
+            if self._pin_sym is None:
+                self._pin_sym = torch.empty(1, dtype=self.sym_stat.dtype).pin_memory()
+            self._pin_sym.copy_(self.sym_stat, non_blocking=True)
         self._pin_stats.copy_(self.stats, non_blocking=True)
         self._pin_lr.copy_(self.optimizer.lr_dev.view(1), non_blocking=True)
         self._pin_ev.record(torch.cuda.current_stream(self.dev))
@@ -817,13 +838,40 @@ class FusedPPOUpdate:
             else:
                 p.grad.copy_(g)
 
-    def _apply_readback(self, s, lr, n):
+    def _apply_readback(self, s, lr, n, sym=None):
         ppo = self.ppo
         if ppo.desired_kl is not None and ppo.schedule == "adaptive":
             ppo.learning_rate = lr
         self.optimizer.param_groups[0]["lr"] = lr
         self.last_losses = (s[2] / n, s[1] / n)
+        if sym is not None:   # the mirror loss's mean symmetry loss
+            ppo.symmetry_loss = sym
         return self.last_losses
+
+    def _mirror_args(self):
+        """What lgx_ppo_loss_bwd_mirror takes beside the loss arguments, for the next minibatch of this
+        update() / gradients() call: (action perm, sign, coeff, ppo_rows, symmetry partials) - the
+        storage's action table, the PPO terms over all rows (augmentation) or the real half, and the
+        minibatch's own slot of symmetry partials (summed once, by _reduce_symmetry_loss)."""
+        ppo, M = self.ppo, self.M
+        per = int(self.lib.lgx_ppo_mirror_partials_floats(M))
+        slots = max(ppo.num_learning_epochs * ppo.num_mini_batches, 1)
+        if self.sym_parts is None or self.sym_parts.numel() != slots * per:
+            self.sym_parts = torch.zeros(slots * per, device=self.dev)
+            self.sym_stat = torch.zeros(1, device=self.dev)
+        if self._sym_slot >= slots:
+            raise RuntimeError("more minibatches than symmetry-loss slots in one update")
+        perm, sign = ppo.storage.symmetry["actions"]
+        parts = C.c_void_p(self.sym_parts.data_ptr() + 4 * self._sym_slot * per)
+        self._sym_slot += 1
+        return _vp(perm), _vp(sign), ppo.mirror_loss_coeff, M if ppo.symmetry_augment else M // 2, parts
+
+    def _reduce_symmetry_loss(self, n):
+        """sym_stat = the mean over the call's n minibatches of L_sym (each a mean over M / 2 rows x A)."""
+        per = int(self.lib.lgx_ppo_mirror_partials_floats(self.M))
+        stream = C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
+        self.check(self.lib.lgx_ppo_mirror_loss_reduce(_vp(self.sym_parts), n * per, 1.0 / (n * (self.M // 2) * self.A),
+                                                       _vp(self.sym_stat), stream), "lgx_ppo_mirror_loss_reduce")
 
     def resolve(self):
         """Apply a deferred update's readback (learning rate, losses); returns its losses, or None
@@ -832,7 +880,8 @@ class FusedPPOUpdate:
         if n is None:
             return None
         self._pin_ev.synchronize()
-        return self._apply_readback(self._pin_stats.tolist(), float(self._pin_lr[0]), n)
+        return self._apply_readback(self._pin_stats.tolist(), float(self._pin_lr[0]), n,
+                                    float(self._pin_sym[0]) if self.ppo.mirror_loss_coeff is not None else None)
 
     def _gather_all(self, indices, obs, cobs, rows, stream):
         """The padded layer-1 input rows of the whole update in minibatch order: per minibatch the
@@ -891,12 +940,15 @@ class FusedPPOUpdate:
         return a
 
     def gradients(self, idx, apply=False):
-        """Flat gradient of one minibatch (rows `idx` of the current storage), for tests."""
+        """Flat gradient of one minibatch (rows `idx` of the current storage), for tests.  With the
+        mirror loss: idx = rows, then the same rows' mirrors (rows + T x N)."""
         if self.recurrent:   # (a recurrent minibatch is whole envs through the memories: update())
             raise NotImplementedError("gradients(idx) takes feed-forward policies; recurrent ones go through update()")
         stream = self._begin_update(idx.numel(), reset=False)
         obs, cobs, storage = self._storage_views()
         self._minibatch(idx, obs, cobs, self._loss_args(storage), stream, apply=apply)
+        if self.ppo.mirror_loss_coeff is not None:   # (sym_stat: this minibatch's L_sym)
+            self._reduce_symmetry_loss(1)
         return self.flat_g.clone()
 
     # ------------------------------------------------------------------ GEMM timing (bench.py)
@@ -1198,7 +1250,11 @@ class FusedPPOUpdate:
             # loss + output-layer backward in one launch; its finalize runs in the reduction
             if self.run.side_on and (L - 1) in self.gemm_dw:
                 self._arm(L - 1)   # (the first join's producer)
-            chk(lib.lgx_ppo_loss_bwd(C.byref(args), _vp(self.head_parts), stream), "lgx_ppo_loss_bwd")
+            if self.ppo.mirror_loss_coeff is not None:   # (the plan runs this launch: checked in _alloc)
+                chk(lib.lgx_ppo_loss_bwd_mirror(C.byref(args), *self._mirror_args(), _vp(self.head_parts), stream),
+                    "lgx_ppo_loss_bwd_mirror")
+            else:
+                chk(lib.lgx_ppo_loss_bwd(C.byref(args), _vp(self.head_parts), stream), "lgx_ppo_loss_bwd")
         else:
             chk(lib.lgx_ppo_loss(C.byref(args), stream), "lgx_ppo_loss")
             # output-layer backward (+ the loss finalize on one extra workgroup of the same launch)

@@ -30,17 +30,28 @@ def _dist():
     return dist if dist.is_available() and dist.is_initialized() and dist.get_world_size() >= least else None
 
 
-def _symmetry_on(cfg):
-    """algorithm.symmetry (None, a dict or a config object) -> whether data augmentation is on;
-    ValueError for the mirror loss or any key this implementation does not know."""
+def _symmetry_cfg(cfg):
+    """algorithm.symmetry (None, a dict or a config object) -> (whether data augmentation is on, the
+    mirror loss's coefficient or None with the mirror loss off).  ValueError for a key this
+    implementation does not know, and for use_mirror_loss = True without a mirror_loss_coeff that
+    is a finite number > 0 (rsl_rl 2.x indexes symmetry_cfg["mirror_loss_coeff"] and fails too).
+    With use_mirror_loss off the coefficient is ignored (rsl_rl 2.x logs a detached symmetry loss
+    then; nothing is computed here)."""
     if cfg is None:
-        return False
+        return False, None
     d = dict(cfg) if isinstance(cfg, dict) else {k: getattr(cfg, k) for k in dir(cfg) if not k.startswith("_")}
-    unknown = sorted(set(d) - {"use_data_augmentation"})
+    unknown = sorted(set(d) - {"use_data_augmentation", "use_mirror_loss", "mirror_loss_coeff"})
     if unknown:
-        raise ValueError(f"symmetry: unsupported key(s) {unknown} (only use_data_augmentation is implemented; the "
-                         "mirror loss is not)")
-    return bool(d.get("use_data_augmentation", False))
+        raise ValueError(f"symmetry: unsupported key(s) {unknown} (use_data_augmentation, use_mirror_loss and "
+                         "mirror_loss_coeff are implemented)")
+    coeff = None
+    if d.get("use_mirror_loss", False):
+        coeff = d.get("mirror_loss_coeff")
+        if isinstance(coeff, bool) or not isinstance(coeff, (int, float)) or not (0.0 < coeff < float("inf")):
+            raise ValueError(f"symmetry: use_mirror_loss = True needs mirror_loss_coeff, a finite number > 0 "
+                             f"(got {coeff!r})")
+        coeff = float(coeff)
+    return bool(d.get("use_data_augmentation", False)), coeff
 
 
 class PPO:
@@ -52,15 +63,23 @@ class PPO:
                  symmetry=None):
         """symmetry: None, or the `algorithm.symmetry` config as a dict (class_to_dict) or an object with
         attributes.  use_data_augmentation = True trains every minibatch on its rollout rows and their
-        left-right mirror images (rsl_rl 2.x symmetry_cfg.use_data_augmentation): the
-        caller then hands the env's tables to init_symmetry() before init_storage().  Off, None and
+        left-right mirror images (rsl_rl 2.x symmetry_cfg.use_data_augmentation).
+        use_mirror_loss = True with mirror_loss_coeff = c adds c x the actor's equivariance defect on
+        every minibatch, mean((mu(mirror(o)) - mirror(mu(o)).detach())^2), to the loss (rsl_rl 2.x
+        symmetry_cfg.use_mirror_loss); without augmentation the PPO terms then run
+        over the rollout rows alone and the mirror rows carry only that term.  With either flag on
+        the caller hands the env's tables to init_symmetry() before init_storage().  Off, None and
         absent all mean nothing changes."""
         self.device = device
-        self.symmetry = _symmetry_on(symmetry)
+        # symmetry: the storage holds the rows' mirror images (either flag); symmetry_augment: the PPO
+        # terms run over them too; mirror_loss_coeff: None, or the mirror loss's coefficient
+        self.symmetry_augment, self.mirror_loss_coeff = _symmetry_cfg(symmetry)
+        self.symmetry = self.symmetry_augment or self.mirror_loss_coeff is not None
         self.symmetry_tables = None
+        self.symmetry_loss = None   # the last update's mean symmetry loss (mirror loss on)
         if self.symmetry and actor_critic.is_recurrent:
-            raise ValueError("symmetry.use_data_augmentation: recurrent policies are not supported (a mirrored "
-                             "trajectory needs its own memory states)")
+            raise ValueError("symmetry.use_data_augmentation / use_mirror_loss: recurrent policies are not supported "
+                             "(a mirrored trajectory needs its own memory states)")
         self.desired_kl = desired_kl
         self.schedule = schedule
         self.learning_rate = learning_rate
@@ -94,8 +113,8 @@ class PPO:
     # ---------------------------------------------------------------- setup / modes
     def init_storage(self, num_envs, num_transitions_per_env, actor_obs_shape, critic_obs_shape, action_shape):
         if self.symmetry and self.symmetry_tables is None:
-            raise ValueError("symmetry.use_data_augmentation is on: call init_symmetry(env.symmetry_tables()) "
-                             "before init_storage()")
+            raise ValueError("symmetry.use_data_augmentation / use_mirror_loss is on: call "
+                             "init_symmetry(env.symmetry_tables()) before init_storage()")
         if self.symmetry:
             for key, shape in (("obs", actor_obs_shape), ("critic_obs", critic_obs_shape), ("actions", action_shape)):
                 t = self.symmetry_tables[key]
@@ -110,7 +129,7 @@ class PPO:
         "actions"} -> (perm int32, sign float32)), moved to this algorithm's device and checked once
         (every perm entry in range, every sign +-1); ValueError with symmetry off."""
         if not self.symmetry:
-            raise ValueError("init_symmetry: symmetry.use_data_augmentation is off")
+            raise ValueError("init_symmetry: symmetry.use_data_augmentation and use_mirror_loss are off")
         tables = {k: None if v is None else (v[0].to(self.device, torch.int32).contiguous(),
                                              v[1].to(self.device, torch.float32).contiguous())
                   for k, v in tables.items()}
@@ -216,6 +235,44 @@ class PPO:
             p.grad.copy_(flat[off:off + n].view_as(p.grad))
             off += n
 
+    def minibatch_loss(self, batch):
+        """The unfused path's forward and loss of one minibatch of the storage's generators -> (loss,
+        value loss, surrogate loss, symmetry loss or None, (mu, sigma, old mu, old sigma) of the rows
+        the PPO terms - and the adaptive schedule's KL - run over)."""
+        obs_b, cobs_b, act_b, target_v_b, adv_b, ret_b, old_logp_b, old_mu_b, old_sigma_b, hid_b, masks_b = batch
+        self.actor_critic.act(obs_b, masks=masks_b, hidden_states=hid_b[0])
+        logp_b = self.actor_critic.get_actions_log_prob(act_b)
+        value_b = self.actor_critic.evaluate(cobs_b, masks=masks_b, hidden_states=hid_b[1])
+        mu_b = self.actor_critic.action_mean
+        sigma_b = self.actor_critic.action_std
+        entropy_b = self.actor_critic.entropy
+        symmetry_loss = None
+        if self.mirror_loss_coeff is not None:
+            # the minibatch is M rollout rows, then their M mirror images: the mirror rows' mean against
+            # the mirrored mean of the rollout rows (the target: no gradient through it)
+            M = mu_b.shape[0] // 2
+            act_perm, act_sign = self.symmetry_tables["actions"]
+            target = mu_b[:M].detach()[:, act_perm.long()] * act_sign
+            symmetry_loss = nn.functional.mse_loss(mu_b[M:], target)
+            if not self.symmetry_augment:   # the PPO terms over the rollout rows alone
+                (logp_b, value_b, mu_b, sigma_b, entropy_b, target_v_b, adv_b, ret_b, old_logp_b, old_mu_b,
+                 old_sigma_b) = (x[:M] for x in (logp_b, value_b, mu_b, sigma_b, entropy_b, target_v_b, adv_b, ret_b,
+                                                 old_logp_b, old_mu_b, old_sigma_b))
+        ratio = torch.exp(logp_b - torch.squeeze(old_logp_b))
+        adv = torch.squeeze(adv_b)
+        surrogate = -adv * ratio
+        surrogate_clipped = -adv * torch.clamp(ratio, 1.0 - self.clip_param, 1.0 + self.clip_param)
+        surrogate_loss = torch.max(surrogate, surrogate_clipped).mean()
+        if self.use_clipped_value_loss:
+            value_clipped = target_v_b + (value_b - target_v_b).clamp(-self.clip_param, self.clip_param)
+            value_loss = torch.max((value_b - ret_b).pow(2), (value_clipped - ret_b).pow(2)).mean()
+        else:
+            value_loss = (ret_b - value_b).pow(2).mean()
+        loss = surrogate_loss + self.value_loss_coef * value_loss - self.entropy_coef * entropy_b.mean()
+        if symmetry_loss is not None:
+            loss = loss + self.mirror_loss_coeff * symmetry_loss
+        return loss, value_loss, surrogate_loss, symmetry_loss, (mu_b, sigma_b, old_mu_b, old_sigma_b)
+
     def update(self, defer=False):
         """rsl_rl PPO.update -> (mean value loss, mean surrogate loss).  defer=True (fused path only)
         issues the update and returns None; resolve() returns the losses later (FusedPPOUpdate)."""
@@ -228,17 +285,15 @@ class PPO:
             return out
         mean_value_loss = 0.0
         mean_surrogate_loss = 0.0
+        mean_symmetry_loss = 0.0
         if self.actor_critic.is_recurrent:
             gen = self.storage.reccurent_mini_batch_generator(self.num_mini_batches, self.num_learning_epochs)
         else:
             gen = self.storage.mini_batch_generator(self.num_mini_batches, self.num_learning_epochs)
-        for (obs_b, cobs_b, act_b, target_v_b, adv_b, ret_b, old_logp_b, old_mu_b, old_sigma_b, hid_b, masks_b) in gen:
-            self.actor_critic.act(obs_b, masks=masks_b, hidden_states=hid_b[0])
-            logp_b = self.actor_critic.get_actions_log_prob(act_b)
-            value_b = self.actor_critic.evaluate(cobs_b, masks=masks_b, hidden_states=hid_b[1])
-            mu_b = self.actor_critic.action_mean
-            sigma_b = self.actor_critic.action_std
-            entropy_b = self.actor_critic.entropy
+        for batch in gen:
+            loss, value_loss, surrogate_loss, symmetry_loss, (mu_b, sigma_b, old_mu_b, old_sigma_b) = \
+                self.minibatch_loss(batch)
+            # (the schedule only sets the step's learning rate: after the loss or before it, as upstream)
             if self.desired_kl is not None and self.schedule == "adaptive":
                 with torch.inference_mode():
                     kl = torch.sum(torch.log(sigma_b / old_sigma_b + 1.e-5) +
@@ -255,17 +310,8 @@ class PPO:
                         self.learning_rate = min(1e-2, self.learning_rate * 1.5)
                     for g in self.optimizer.param_groups:
                         g["lr"] = self.learning_rate
-            ratio = torch.exp(logp_b - torch.squeeze(old_logp_b))
-            adv = torch.squeeze(adv_b)
-            surrogate = -adv * ratio
-            surrogate_clipped = -adv * torch.clamp(ratio, 1.0 - self.clip_param, 1.0 + self.clip_param)
-            surrogate_loss = torch.max(surrogate, surrogate_clipped).mean()
-            if self.use_clipped_value_loss:
-                value_clipped = target_v_b + (value_b - target_v_b).clamp(-self.clip_param, self.clip_param)
-                value_loss = torch.max((value_b - ret_b).pow(2), (value_clipped - ret_b).pow(2)).mean()
-            else:
-                value_loss = (ret_b - value_b).pow(2).mean()
-            loss = surrogate_loss + self.value_loss_coef * value_loss - self.entropy_coef * entropy_b.mean()
+            if symmetry_loss is not None:
+                mean_symmetry_loss += symmetry_loss.detach()
             self.optimizer.zero_grad()
             loss.backward()
             if self.dist is not None:
@@ -279,6 +325,8 @@ class PPO:
         n = self.num_learning_epochs * self.num_mini_batches
         mean_value_loss = (mean_value_loss / n).item()
         mean_surrogate_loss = (mean_surrogate_loss / n).item()
+        if self.mirror_loss_coeff is not None:
+            self.symmetry_loss = (mean_symmetry_loss / n).item()
         self.storage.clear()
         if defer:
             self._deferred = (mean_value_loss, mean_surrogate_loss)

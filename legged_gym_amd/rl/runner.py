@@ -41,10 +41,10 @@ class OnPolicyRunner:
         actor_critic = ac_class(self.env.num_obs, num_critic_obs, self.env.num_actions, **self.policy_cfg).to(self.device)
         alg_class = {"PPO": PPO}[self.cfg["algorithm_class_name"]]
         self.alg = alg_class(actor_critic, device=self.device, **self.alg_cfg)
-        if getattr(self.alg, "symmetry", False):   # algorithm.symmetry.use_data_augmentation
+        if getattr(self.alg, "symmetry", False):   # algorithm.symmetry.use_data_augmentation / use_mirror_loss
             if self.cfg.get("empirical_normalization", False):
-                raise ValueError("symmetry.use_data_augmentation with runner.empirical_normalization: the storage "
-                                 "holds normalised rows, and per-column statistics are not mirror-symmetric")
+                raise ValueError("symmetry.use_data_augmentation / use_mirror_loss with runner.empirical_normalization: "
+                                 "the storage holds normalised rows, and per-column statistics are not mirror-symmetric")
             self.alg.init_symmetry(self.env.symmetry_tables())
         self.num_steps_per_env = self.cfg["num_steps_per_env"]
         self.save_interval = self.cfg["save_interval"]
@@ -183,13 +183,13 @@ class OnPolicyRunner:
                     learn_time = ev[1].elapsed_time(ev[2]) * 1e-3
                 self.last_iteration_stats = dict(collection_time=collection_time, learn_time=learn_time,
                                                  value_loss=mean_value_loss, surrogate_loss=mean_surrogate_loss,
-                                                 learning_rate=self.alg.learning_rate)
+                                                 learning_rate=self.alg.learning_rate, **self._symmetry_stats())
                 if logged:
                     rewbuffer, lenbuffer = stats.result(ticket)
                     self.log(dict(it=it, num_learning_iterations=num_learning_iterations, ep_infos=ep_infos,
                                   collection_time=collection_time, learn_time=learn_time,
                                   mean_value_loss=mean_value_loss, mean_surrogate_loss=mean_surrogate_loss,
-                                  rewbuffer=rewbuffer, lenbuffer=lenbuffer))
+                                  rewbuffer=rewbuffer, lenbuffer=lenbuffer, **self._symmetry_stats()))
                     if it % self.save_interval == 0:
                         self.save(os.path.join(self.log_dir, f"model_{it}.pt"))
                 ep_infos.clear()
@@ -225,12 +225,19 @@ class OnPolicyRunner:
         self.last_iteration_stats = dict(collection_time=ev[0].elapsed_time(ev[1]) * 1e-3,
                                          learn_time=ev[1].elapsed_time(ev[2]) * 1e-3,
                                          value_loss=mean_value_loss, surrogate_loss=mean_surrogate_loss,
-                                         learning_rate=self.alg.learning_rate)
+                                         learning_rate=self.alg.learning_rate, **self._symmetry_stats())
         if locs is not None and log:
             rewbuffer, lenbuffer = locs.pop("stats").result(locs.pop("ticket"))
             self.log(dict(locs, collection_time=self.last_iteration_stats["collection_time"],
                           learn_time=self.last_iteration_stats["learn_time"], mean_value_loss=mean_value_loss,
-                          mean_surrogate_loss=mean_surrogate_loss, rewbuffer=rewbuffer, lenbuffer=lenbuffer))
+                          mean_surrogate_loss=mean_surrogate_loss, rewbuffer=rewbuffer, lenbuffer=lenbuffer,
+                          **self._symmetry_stats()))
+
+    def _symmetry_stats(self):
+        """{"symmetry_loss": the last (resolved) update's mean symmetry loss} with the mirror loss on, else {}."""
+        if getattr(self.alg, "mirror_loss_coeff", None) is None:
+            return {}
+        return {"symmetry_loss": self.alg.symmetry_loss}
 
     def _log_values(self, ep_infos, defer=False):
         """What log() reads from the device, in one reduction and one readback: the mean over the
@@ -273,6 +280,8 @@ class OnPolicyRunner:
         if w:
             w.add_scalar("Loss/value_function", locs["mean_value_loss"], locs["it"])
             w.add_scalar("Loss/surrogate", locs["mean_surrogate_loss"], locs["it"])
+            if "symmetry_loss" in locs:
+                w.add_scalar("Loss/symmetry", locs["symmetry_loss"], locs["it"])
             w.add_scalar("Loss/learning_rate", self.alg.learning_rate, locs["it"])
             w.add_scalar("Policy/mean_noise_std", noise_std, locs["it"])
             w.add_scalar("Perf/total_fps", fps, locs["it"])
@@ -283,6 +292,8 @@ class OnPolicyRunner:
         s += f"{'Computation:':>{pad}} {fps:.0f} steps/s (collection: {locs['collection_time']:.3f}s, learning {locs['learn_time']:.3f}s)\n"
         s += f"{'Value function loss:':>{pad}} {locs['mean_value_loss']:.4f}\n"
         s += f"{'Surrogate loss:':>{pad}} {locs['mean_surrogate_loss']:.4f}\n"
+        if "symmetry_loss" in locs:
+            s += f"{'Symmetry loss:':>{pad}} {locs['symmetry_loss']:.4f}\n"
         s += f"{'Mean action noise std:':>{pad}} {noise_std:.2f}\n"
         if len(locs["rewbuffer"]) > 0:
             s += f"{'Mean reward:':>{pad}} {statistics.mean(locs['rewbuffer']):.2f}\n"

@@ -311,6 +311,9 @@ SIGS_PRODUCT = {  # PPO update entry points and the later features: product libr
     "obs_norm_apply": (C.c_int, [C.POINTER(LgxObsNormJob), i32, vp]),
     "ppo_symmetry_augment": (C.c_int, [C.POINTER(LgxSymmetryArgs), vp]),
     "ppo_symmetry_check_table": (C.c_int, [vp, vp, i32]),
+    "ppo_loss_bwd_mirror": (C.c_int, [C.POINTER(LgxPpoLossArgs), vp, vp, C.c_float, i64, vp, vp, vp]),
+    "ppo_mirror_partials_floats": (i64, [i64]),
+    "ppo_mirror_loss_reduce": (C.c_int, [vp, i64, C.c_float, vp, vp]),
 }
 SIGS = {**SIGS_COMMON, **SIGS_PRODUCT}
 EXPORTED = [f"lgx_{name}" for name in SIGS]
