@@ -1038,6 +1038,28 @@ int lgx_ppo_loss_bwd_mirror(const lgx_ppo_loss_args* args, const int32_t* act_pe
 int64_t lgx_ppo_mirror_partials_floats(int64_t rows);
 int lgx_ppo_mirror_loss_reduce(const float* partials, int64_t count, float scale, float* out, void* stream);
 
+/* Teacher-student distillation (rsl_rl 2.x Distillation, loss_type "mse"; lgx_distill.hip): the
+ * student's output layer, the behaviour loss and the output layer's backward in ONE launch over
+ * 32-row chunks.  head_in [rows, hidden] (the last hidden layer's ELU output, hidden % 16 == 0,
+ * 16-byte aligned) is overwritten by dZ3:
+ *   mu = head_in W4^T + b4 (W4 [A, hidden]),  d = mu - target (target [rows, A]),
+ *   loss_partials[w] = the sum of d^2 over workgroup w's rows (unscaled),
+ *   d mu = 2 * scale * d (scale = 1 / (N * A) of the update),  dZ3 = (d mu W4) * ELU'(head_in),
+ *   head_partials[w] = [A*hidden dW4 | A db4 | hidden db3] of workgroup w's rows (lgx_reduce_slices
+ *   sums the chunks).
+ * lgx_bc_loss_bwd_layout: out[0] = floats of loss_partials (the workgroups), out[1] = floats of
+ * head_partials, out[2] = dynamic LDS bytes.  rows need not be a multiple of 32.  No float atomics:
+ * two launches give the same bits.  LGX_EINVAL (message in lgx_last_error, nothing launched) for a
+ * null pointer, rows < 1, num_actions outside [1, LGX_PPO_MAX_ACTIONS], hidden not a positive
+ * multiple of 16 or too wide for 96 KB of LDS, head_in / W4 not 16-byte aligned, a scale that is
+ * not finite.  lgx_bc_loss_reduce: out[0] = scale * the sum of `count` partials, one workgroup,
+ * fixed order (once per update, over every chunk's loss partials). */
+int lgx_bc_loss_bwd_layout(int64_t rows, int32_t num_actions, int32_t hidden, int64_t out[3]);
+int lgx_bc_loss_bwd(float* head_in, const float* W4, const float* b4, const float* target, int64_t rows,
+                    int32_t num_actions, int32_t hidden, float scale, float* loss_partials, float* head_partials,
+                    void* stream);
+int lgx_bc_loss_reduce(const float* partials, int64_t count, float scale, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,7 +7,10 @@ an observation history: cfg.history), go1_rough_actrand (go1_rough with per-env 
 action latency: cfg.actuator_rand), go1_rough_cmdcur (go1_rough with the command curriculum:
 commands.curriculum, lin_vel_x widening from half of go1_rough's range), go1_rough_sym (go1_rough
 trained with left-right symmetry data augmentation: algorithm.symmetry), go1_rough_mirror (go1_rough
-trained with the symmetry mirror loss: algorithm.symmetry.use_mirror_loss), go1_flat_bench (C2 as
+trained with the symmetry mirror loss: algorithm.symmetry.use_mirror_loss), go1_rough_teacher
+(go1_rough_asym with runner.privileged_actor: actor and critic read the privileged row),
+go1_rough_distill (teacher-student distillation of such a teacher into a student on the 475-wide
+history row: Distillation + StudentTeacher), go1_flat_bench (C2 as
 BASELINE states it: PD, no domain randomisation), anymal_c_rough (C5), anymal_c_flat, and the
 remaining robots of the reference registry: anymal_b, a1, a1_src, aliengo and cassie (the biped:
 2 legs x 6 joints on the dense physics kernel).
@@ -26,9 +29,10 @@ from .cassie.cassie import Cassie
 from .cassie.cassie_config import CassieRoughCfg, CassieRoughCfgPPO
 from .base.legged_robot_config import LeggedRobotCfg, LeggedRobotCfgPPO
 from .go1.go1 import Go1
-from .go1.go1_config import (Go1FlatBenchCfg, Go1RoughActRandCfg, Go1RoughAsymCfg, Go1RoughCfg, Go1RoughCfgPPO,
-                             Go1RoughCmdCurCfg, Go1RoughHistCfg, Go1RoughMirrorCfgPPO, Go1RoughNormCfgPPO,
-                             Go1RoughSymCfgPPO, Go1RoughSymMirrorCfgPPO, Go1RoughTerrainCfg)
+from .go1.go1_config import (Go1FlatBenchCfg, Go1RoughActRandCfg, Go1RoughAsymCfg, Go1RoughAsymHistCfg, Go1RoughCfg,
+                             Go1RoughCfgPPO, Go1RoughCmdCurCfg, Go1RoughDistillCfgPPO, Go1RoughHistCfg,
+                             Go1RoughMirrorCfgPPO, Go1RoughNormCfgPPO, Go1RoughSymCfgPPO, Go1RoughSymMirrorCfgPPO,
+                             Go1RoughTeacherCfgPPO, Go1RoughTerrainCfg)
 
 task_registry.register("go1", Go1, Go1RoughCfg(), Go1RoughCfgPPO())
 task_registry.register("go1_flat_bench", Go1, Go1FlatBenchCfg(), Go1RoughCfgPPO())
@@ -51,3 +55,10 @@ task_registry.register_variant("go1_rough_cmdcur", "go1_rough", Go1RoughCfgPPO()
 task_registry.register_variant("go1_rough_sym", "go1_rough", Go1RoughSymCfgPPO())
 # go1_rough trained with the mirror loss on the actor's equivariance defect: the same env, another train cfg
 task_registry.register_variant("go1_rough_mirror", "go1_rough", Go1RoughMirrorCfgPPO())
+# go1_rough_asym with the privileged row as the actor's observations too: a teacher for go1_rough_distill
+task_registry.register_variant("go1_rough_teacher", "go1_rough_asym", Go1RoughTeacherCfgPPO())
+# the teacher distilled into a student that reads the observation history (475), the teacher the privileged row (253)
+# (the same env class, Go1, with an env cfg of its own: a variant, so go1_rough_asym stays the one registered env
+# with a privileged row and go1_rough_hist the one with a history)
+task_registry.register_variant("go1_rough_distill", "go1_rough_asym", Go1RoughDistillCfgPPO(),
+                               env_cfg=Go1RoughAsymHistCfg())

@@ -6,7 +6,8 @@ with the 187-point height scan (235-dim obs), as SURVEY.md §8 defines it.
 `Go1RoughAsymCfg` is that task with an asymmetric actor-critic: the critic reads the privileged
 row (noise-free observations + the randomised friction / base mass + foot contacts).
 `Go1RoughHistCfg` is go1_rough with an observation history, registered as
-go1_rough_hist; `Go1RoughAsymHistCfg` pairs the history with the privileged critic (not registered).
+go1_rough_hist; `Go1RoughAsymHistCfg` pairs the history with the privileged critic (the env of the
+go1_rough_distill variant; not a registered env of its own).
 `Go1RoughActRandCfg` is go1_rough with per-env drive gains and action latency,
 registered as go1_rough_actrand.
 `Go1RoughCmdCurCfg` is go1_rough with the command curriculum, registered as
@@ -17,6 +18,9 @@ privileged critic) meant to be trained with it (not registered).
 `Go1RoughMirrorCfgPPO` trains with the symmetry mirror loss alone: go1_rough under it is
 registered as go1_rough_mirror; `Go1RoughSymMirrorCfgPPO` pairs the mirror loss with the augmentation (not
 registered).
+`Go1RoughTeacherCfgPPO` trains a privileged teacher (runner.privileged_actor; go1_rough_asym under it is
+go1_rough_teacher) and `Go1RoughDistillCfgPPO` distils it into a student on the history row
+(Go1RoughAsymHistCfg under it is go1_rough_distill).
 """
 from legged_gym_amd.envs.base.legged_robot_config import LeggedRobotCfg, LeggedRobotCfgPPO
 
@@ -185,9 +189,9 @@ class Go1RoughCmdCurCfg(Go1RoughTerrainCfg):
 
 class Go1RoughAsymHistCfg(Go1RoughAsymCfg):
     """go1_rough_asym with that history for the actor: actor 475 wide, critic the 253-wide privileged
-    row.  Not in the registry (go1_rough_asym is the one registered task with a privileged row);
-    register it under a name of your own: task_registry.register(name, Go1, Go1RoughAsymHistCfg(),
-    Go1RoughCfgPPO())."""
+    row.  Not a registered env (go1_rough_asym is the one registered env with a privileged row; the
+    go1_rough_distill variant trains on this cfg); to train PPO on it register it under a name of
+    your own: task_registry.register(name, Go1, Go1RoughAsymHistCfg(), Go1RoughCfgPPO())."""
     class history(Go1RoughAsymCfg.history):
         frames = 5
 
@@ -197,3 +201,40 @@ class Go1RoughAsymHistSymCfg(Go1RoughAsymHistCfg):
     critic, to be trained under Go1RoughSymCfgPPO: all three mirror tables (history frames, privileged
     tail, actions) are in use.  Not in the registry: task_registry.register(name, Go1,
     Go1RoughAsymHistSymCfg(), Go1RoughSymCfgPPO())."""
+
+
+class Go1RoughTeacherCfgPPO(Go1RoughCfgPPO):
+    """Go1RoughCfgPPO training a privileged teacher: the env's privileged row is the
+    one observation row of actor and critic.  go1_rough_asym under it is registered as
+    go1_rough_teacher; its checkpoints are what go1_rough_distill loads."""
+    class runner(Go1RoughCfgPPO.runner):
+        privileged_actor = True
+        experiment_name = 'rough_go1_teacher'
+
+
+class Go1RoughDistillCfgPPO(LeggedRobotCfgPPO):
+    """Teacher-student distillation (rsl_rl 2.x Distillation + StudentTeacher): the
+    student reads the 475-wide history row of Go1RoughAsymHistCfg, the teacher - a go1_rough_teacher
+    checkpoint's actor - the 253-wide privileged row.  Registered as go1_rough_distill:
+        --task go1_rough_distill --resume --load_run <a go1_rough_teacher run>
+    (both tasks log under rough_go1_teacher, so --load_run finds the teacher's run).  Every value
+    below is untuned: no distilled student has been evaluated."""
+    class policy:
+        init_noise_std = 0.1
+        student_hidden_dims = [512, 256, 128]
+        teacher_hidden_dims = [512, 256, 128]   # the teacher run's actor_hidden_dims
+        activation = 'elu'
+
+    class algorithm:
+        num_learning_epochs = 1
+        gradient_length = 12
+        learning_rate = 1.e-3
+        max_grad_norm = None
+        loss_type = 'mse'
+
+    class runner(LeggedRobotCfgPPO.runner):
+        policy_class_name = 'StudentTeacher'
+        algorithm_class_name = 'Distillation'
+        num_steps_per_env = 24
+        run_name = ''
+        experiment_name = 'rough_go1_teacher'

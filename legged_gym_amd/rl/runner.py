@@ -15,6 +15,16 @@ object when the env has no privileged row).  learn() normalises each step's rows
 env.step, with an update; the storage, the returns and the update then see normalised rows.  The
 checkpoint gains `obs_norm_state_dict` (and `critic_obs_norm_state_dict` for a separate critic
 normaliser), and load() refuses a checkpoint from the other side of the flag.
+
+`runner.privileged_actor = True` (read like empirical_normalization: a dict without it is off)
+trains a teacher: the env's privileged row is the one observation row of actor and critic
+(`ActorCritic(num_priv, num_priv, A)`, stored once), and get_inference_policy() expects that row.
+
+`algorithm_class_name = "Distillation"` with `policy_class_name = "StudentTeacher"`
+runs the same loop: the student acts on the env's observations, the teacher labels the privileged
+row, `Loss/behavior` replaces the value and surrogate losses, and load() follows
+StudentTeacher.load_state_dict: a PPO checkpoint only provides the teacher (iteration 0, fresh
+optimizer), a distillation checkpoint resumes.
 """
 import os
 import statistics
@@ -25,7 +35,9 @@ import torch
 from .actor_critic import ActorCritic, ActorCriticRecurrent  # noqa: F401  (resolved by name from the cfg)
 from .episode_stats import EpisodeStats
 from .normalizer import EmpiricalNormalization, normalize_many
+from .distillation import Distillation
 from .ppo import PPO  # noqa: F401
+from .student_teacher import StudentTeacher
 
 
 class OnPolicyRunner:
@@ -36,10 +48,18 @@ class OnPolicyRunner:
         self.device = device
         self.env = env
         num_critic_obs = self.env.num_privileged_obs if self.env.num_privileged_obs is not None else self.env.num_obs
-        ac_class = {"ActorCritic": ActorCritic,
-                    "ActorCriticRecurrent": ActorCriticRecurrent}[self.cfg["policy_class_name"]]
-        actor_critic = ac_class(self.env.num_obs, num_critic_obs, self.env.num_actions, **self.policy_cfg).to(self.device)
-        alg_class = {"PPO": PPO}[self.cfg["algorithm_class_name"]]
+        ac_class = {"ActorCritic": ActorCritic, "ActorCriticRecurrent": ActorCriticRecurrent,
+                    "StudentTeacher": StudentTeacher}[self.cfg["policy_class_name"]]
+        alg_class = {"PPO": PPO, "Distillation": Distillation}[self.cfg["algorithm_class_name"]]
+        self.distillation = alg_class is Distillation
+        # the privileged row as the env's one observation row (a teacher for Distillation)
+        self.privileged_actor = bool(self.cfg.get("privileged_actor", False))
+        num_actor_obs = self.env.num_obs
+        if self.privileged_actor or self.distillation:
+            self._check_teacher_student_cfg(ac_class)
+        if self.privileged_actor:
+            num_actor_obs = num_critic_obs
+        actor_critic = ac_class(num_actor_obs, num_critic_obs, self.env.num_actions, **self.policy_cfg).to(self.device)
         self.alg = alg_class(actor_critic, device=self.device, **self.alg_cfg)
         if getattr(self.alg, "symmetry", False):   # algorithm.symmetry.use_data_augmentation / use_mirror_loss
             if self.cfg.get("empirical_normalization", False):
@@ -48,8 +68,8 @@ class OnPolicyRunner:
             self.alg.init_symmetry(self.env.symmetry_tables())
         self.num_steps_per_env = self.cfg["num_steps_per_env"]
         self.save_interval = self.cfg["save_interval"]
-        self.alg.init_storage(self.env.num_envs, self.num_steps_per_env, [self.env.num_obs],
-                              [self.env.num_privileged_obs], [self.env.num_actions])
+        self.alg.init_storage(self.env.num_envs, self.num_steps_per_env, [num_actor_obs],
+                              [None if self.privileged_actor else self.env.num_privileged_obs], [self.env.num_actions])
         self.obs_normalizer = self.critic_obs_normalizer = None
         if self.cfg.get("empirical_normalization", False):
             until = self.cfg.get("empirical_normalization_until")
@@ -64,6 +84,37 @@ class OnPolicyRunner:
         self.current_learning_iteration = 0
         self.last_iteration_stats = {}
         _, _ = self.env.reset()
+
+    def _check_teacher_student_cfg(self, ac_class):
+        """The refusals of runner.privileged_actor and of Distillation (each names its key)."""
+        what = "runner.privileged_actor" if self.privileged_actor else "algorithm_class_name = \"Distillation\""
+        if self.env.num_privileged_obs is None:
+            raise ValueError(f"{what} needs an env with a privileged row (env.num_privileged_obs is None)")
+        if self.cfg.get("empirical_normalization", False):
+            raise ValueError(f"runner.empirical_normalization is not supported with {what}")
+        if self.privileged_actor and self.distillation:
+            raise ValueError("runner.privileged_actor trains a PPO teacher; Distillation reads the privileged row itself")
+        if self.distillation != (ac_class is StudentTeacher):
+            raise ValueError("algorithm_class_name = \"Distillation\" and policy_class_name = \"StudentTeacher\" "
+                             "go together")
+        if self.privileged_actor:
+            sym = self.alg_cfg.get("symmetry") or {}
+            if sym.get("use_data_augmentation", False) or sym.get("use_mirror_loss", False):
+                raise ValueError("algorithm.symmetry is not supported with runner.privileged_actor (the observation "
+                                 "table does not mirror the privileged row)")
+
+    def _rows(self, obs, privileged_obs):
+        """(actor rows, critic rows) of an env step: the observations and the privileged row (the
+        observations again without one); runner.privileged_actor: the privileged row for both."""
+        critic_obs = privileged_obs if privileged_obs is not None else obs
+        return (critic_obs if self.privileged_actor else obs), critic_obs
+
+    def _loss_locs(self, losses):
+        """An update's result as log()'s entries: PPO's (mean value loss, mean surrogate loss), or
+        Distillation's mean behaviour loss."""
+        if self.distillation:
+            return {"mean_behavior_loss": losses}
+        return {"mean_value_loss": losses[0], "mean_surrogate_loss": losses[1]}
 
     def _writer(self):
         if self.writer is None and self.log_dir is not None:
@@ -91,7 +142,7 @@ class OnPolicyRunner:
                                                              high=int(self.env.max_episode_length))
         obs = self.env.get_observations()
         privileged_obs = self.env.get_privileged_observations()
-        critic_obs = privileged_obs if privileged_obs is not None else obs
+        obs, critic_obs = self._rows(obs, privileged_obs)
         obs, critic_obs = obs.to(self.device), critic_obs.to(self.device)
         normalizing = self.obs_normalizer is not None
         if normalizing:
@@ -141,7 +192,7 @@ class OnPolicyRunner:
                     for _ in range(self.num_steps_per_env):
                         actions = self.alg.act(obs, critic_obs)
                         obs, privileged_obs, rewards, dones, infos = self.env.step(actions)
-                        critic_obs = privileged_obs if privileged_obs is not None else obs
+                        obs, critic_obs = self._rows(obs, privileged_obs)
                         obs, critic_obs = obs.to(self.device), critic_obs.to(self.device)
                         if normalizing:
                             obs, critic_obs = self._normalize(obs, critic_obs)
@@ -173,7 +224,7 @@ class OnPolicyRunner:
                         ep_infos = []
                     ep_infos.clear()
                     continue
-                mean_value_loss, mean_surrogate_loss = self.alg.update()
+                losses = self._loss_locs(self.alg.update())
                 stop = time.time()
                 learn_time = stop - start
                 if cuda:
@@ -182,13 +233,12 @@ class OnPolicyRunner:
                     collection_time = ev[0].elapsed_time(ev[1]) * 1e-3
                     learn_time = ev[1].elapsed_time(ev[2]) * 1e-3
                 self.last_iteration_stats = dict(collection_time=collection_time, learn_time=learn_time,
-                                                 value_loss=mean_value_loss, surrogate_loss=mean_surrogate_loss,
+                                                 **{k[len("mean_"):]: v for k, v in losses.items()},
                                                  learning_rate=self.alg.learning_rate, **self._symmetry_stats())
                 if logged:
                     rewbuffer, lenbuffer = stats.result(ticket)
                     self.log(dict(it=it, num_learning_iterations=num_learning_iterations, ep_infos=ep_infos,
-                                  collection_time=collection_time, learn_time=learn_time,
-                                  mean_value_loss=mean_value_loss, mean_surrogate_loss=mean_surrogate_loss,
+                                  collection_time=collection_time, learn_time=learn_time, **losses,
                                   rewbuffer=rewbuffer, lenbuffer=lenbuffer, **self._symmetry_stats()))
                     if it % self.save_interval == 0:
                         self.save(os.path.join(self.log_dir, f"model_{it}.pt"))
@@ -220,17 +270,17 @@ class OnPolicyRunner:
         phase times from its stream events (all complete by the time the next rollout is issued);
         then its log entry (LGX_DEFER_LOG=1)."""
         ev, locs = pending
-        mean_value_loss, mean_surrogate_loss = self.alg.resolve()
+        losses = self._loss_locs(self.alg.resolve())
         ev[2].synchronize()
         self.last_iteration_stats = dict(collection_time=ev[0].elapsed_time(ev[1]) * 1e-3,
                                          learn_time=ev[1].elapsed_time(ev[2]) * 1e-3,
-                                         value_loss=mean_value_loss, surrogate_loss=mean_surrogate_loss,
+                                         **{k[len("mean_"):]: v for k, v in losses.items()},
                                          learning_rate=self.alg.learning_rate, **self._symmetry_stats())
         if locs is not None and log:
             rewbuffer, lenbuffer = locs.pop("stats").result(locs.pop("ticket"))
             self.log(dict(locs, collection_time=self.last_iteration_stats["collection_time"],
-                          learn_time=self.last_iteration_stats["learn_time"], mean_value_loss=mean_value_loss,
-                          mean_surrogate_loss=mean_surrogate_loss, rewbuffer=rewbuffer, lenbuffer=lenbuffer,
+                          learn_time=self.last_iteration_stats["learn_time"], **losses, rewbuffer=rewbuffer,
+                          lenbuffer=lenbuffer,
                           **self._symmetry_stats()))
 
     def _symmetry_stats(self):
@@ -278,8 +328,11 @@ class OnPolicyRunner:
                 lines.append(f"{'Mean episode ' + key + ':':>{pad}} {value:.4f}")
         fps = int(self.num_steps_per_env * self.env.num_envs / it_time)
         if w:
-            w.add_scalar("Loss/value_function", locs["mean_value_loss"], locs["it"])
-            w.add_scalar("Loss/surrogate", locs["mean_surrogate_loss"], locs["it"])
+            if "mean_behavior_loss" in locs:
+                w.add_scalar("Loss/behavior", locs["mean_behavior_loss"], locs["it"])
+            else:
+                w.add_scalar("Loss/value_function", locs["mean_value_loss"], locs["it"])
+                w.add_scalar("Loss/surrogate", locs["mean_surrogate_loss"], locs["it"])
             if "symmetry_loss" in locs:
                 w.add_scalar("Loss/symmetry", locs["symmetry_loss"], locs["it"])
             w.add_scalar("Loss/learning_rate", self.alg.learning_rate, locs["it"])
@@ -290,8 +343,11 @@ class OnPolicyRunner:
         header = f" \033[1m Learning iteration {locs['it']}/{self.current_learning_iteration + locs['num_learning_iterations']} \033[0m "
         s = f"{'#' * width}\n{header.center(width, ' ')}\n\n"
         s += f"{'Computation:':>{pad}} {fps:.0f} steps/s (collection: {locs['collection_time']:.3f}s, learning {locs['learn_time']:.3f}s)\n"
-        s += f"{'Value function loss:':>{pad}} {locs['mean_value_loss']:.4f}\n"
-        s += f"{'Surrogate loss:':>{pad}} {locs['mean_surrogate_loss']:.4f}\n"
+        if "mean_behavior_loss" in locs:
+            s += f"{'Behavior loss:':>{pad}} {locs['mean_behavior_loss']:.4f}\n"
+        else:
+            s += f"{'Value function loss:':>{pad}} {locs['mean_value_loss']:.4f}\n"
+            s += f"{'Surrogate loss:':>{pad}} {locs['mean_surrogate_loss']:.4f}\n"
         if "symmetry_loss" in locs:
             s += f"{'Symmetry loss:':>{pad}} {locs['symmetry_loss']:.4f}\n"
         s += f"{'Mean action noise std:':>{pad}} {noise_std:.2f}\n"
@@ -327,9 +383,11 @@ class OnPolicyRunner:
             self.obs_normalizer.load_state_dict(d["obs_norm_state_dict"])
             if separate:
                 self.critic_obs_normalizer.load_state_dict(d["critic_obs_norm_state_dict"])
-        self.alg.actor_critic.load_state_dict(d["model_state_dict"])
+        resumed = self.alg.actor_critic.load_state_dict(d["model_state_dict"])
         if hasattr(self.alg.actor_critic, "invalidate_fused"):
             self.alg.actor_critic.invalidate_fused()
+        if resumed is False:   # StudentTeacher took a PPO checkpoint's actor as its teacher: not a resumed run
+            return d["infos"]
         if load_optimizer:
             # as upstream rsl_rl: the optimizer state (its param_groups' lr included) is restored and
             # alg.learning_rate keeps the config value - the adaptive schedule's first update then
@@ -340,6 +398,8 @@ class OnPolicyRunner:
         return d["infos"]
 
     def get_inference_policy(self, device=None):
+        """The deployable policy: observations -> action means.  runner.privileged_actor: it expects
+        the env's privileged row (env.get_privileged_observations()); Distillation: the student."""
         self.alg.actor_critic.eval()
         if device is not None:
             self.alg.actor_critic.to(device)

@@ -37,11 +37,14 @@ def play(args, steps=1000):
     env_cfg.commands.ranges.lin_vel_y = [0.5, 0.5]
     env_cfg.commands.ranges.heading = [-1.57, -1.57]
     env, _ = task_registry.make_env(name=args.task, args=args, env_cfg=env_cfg)
-    obs = env.get_observations()
+    # runner.privileged_actor (a teacher, e.g. go1_rough_teacher): the policy reads the privileged row
+    privileged_actor = bool(getattr(train_cfg.runner, "privileged_actor", False))
+    obs = env.get_privileged_observations() if privileged_actor else env.get_observations()
     train_cfg.runner.resume = True
     ppo_runner, train_cfg = task_registry.make_alg_runner(env=env, name=args.task, args=args, train_cfg=train_cfg)
     policy = ppo_runner.get_inference_policy(device=env.device)
-    if EXPORT_POLICY:
+    distilled = hasattr(ppo_runner.alg.actor_critic, "student")   # (StudentTeacher: no `actor` to export)
+    if EXPORT_POLICY and not distilled:
         path = os.path.join(LEGGED_GYM_ROOT_DIR, "logs", train_cfg.runner.experiment_name, "exported", "policies")
         export_policy_as_jit(ppo_runner.alg.actor_critic, path, normalizer=ppo_runner.obs_normalizer)
         print("Exported policy as jit script to: ", path)
@@ -55,7 +58,9 @@ def play(args, steps=1000):
     for i in range(steps):
         with torch.inference_mode():
             actions = policy(obs.detach())
-            obs, _, rews, dones, infos = env.step(actions.detach())
+            obs, privileged_obs, rews, dones, infos = env.step(actions.detach())
+            if privileged_actor:
+                obs = privileged_obs
         ep_rew += rews
         if dones.any():
             finished += ep_rew[dones].tolist()
@@ -76,7 +81,7 @@ def play(args, steps=1000):
                 "contact_forces_z": env.contact_forces[robot_index, env.feet_indices, 2].cpu().numpy(),
             })
         elif i == stop_state_log:
-            png = logger.plot_states(os.path.join(path if EXPORT_POLICY else ".", "states.png"))
+            png = logger.plot_states(os.path.join(path if EXPORT_POLICY and not distilled else ".", "states.png"))
             print("State plots written to:", png)
         if 0 < i < stop_rew_log:                          # play.py:112-118
             if infos["episode"]:

@@ -314,6 +314,9 @@ SIGS_PRODUCT = {  # PPO update entry points and the later features: product libr
     "ppo_loss_bwd_mirror": (C.c_int, [C.POINTER(LgxPpoLossArgs), vp, vp, C.c_float, i64, vp, vp, vp]),
     "ppo_mirror_partials_floats": (i64, [i64]),
     "ppo_mirror_loss_reduce": (C.c_int, [vp, i64, C.c_float, vp, vp]),
+    "bc_loss_bwd_layout": (C.c_int, [i64, i32, i32, C.POINTER(i64)]),
+    "bc_loss_bwd": (C.c_int, [vp, vp, vp, vp, i64, i32, i32, C.c_float, vp, vp, vp]),
+    "bc_loss_reduce": (C.c_int, [vp, i64, C.c_float, vp, vp]),
 }
 SIGS = {**SIGS_COMMON, **SIGS_PRODUCT}
 EXPORTED = [f"lgx_{name}" for name in SIGS]

@@ -3,6 +3,7 @@ directory) and as bench.py runs it (without): go1_rough (or --task), 4096 envs.
 
     python tools/train_time.py [--configs logged,logged_old,logged_defer,unlogged] [--iters 50]
                                [--warmup 10] [--windows 5] [--task go1_rough]
+                               [--no_fused_update] [--teacher CHECKPOINT]
 
 Configurations (one runner with a temporary log directory, one without, on one env):
     logged        log directory, device episode statistics (the default path)
@@ -15,6 +16,8 @@ its end).  The windows of the configurations alternate, after learn(warmup) of e
 JSON line: per configuration the median ms per iteration and every window's, the last iteration's
 collection / learn phases, and for a task with symmetry augmentation (go1_rough_sym) the augment
 launch's time from HIP events around it.
+--no_fused_update times the autograd update (algorithm.use_fused_update = False); a Distillation task
+(go1_rough_distill) takes its teacher from --teacher or keeps a randomly initialised one.
 """
 import argparse
 import contextlib
@@ -43,6 +46,11 @@ def main():
     ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--num_envs", type=int, default=4096)
     ap.add_argument("--task", default="go1_rough")
+    ap.add_argument("--no_fused_update", action="store_true",
+                    help="algorithm.use_fused_update = False: the autograd update (the fused update's yardstick)")
+    ap.add_argument("--teacher", default=None,
+                    help="Distillation tasks: a go1_rough_teacher checkpoint; without one the teacher keeps its "
+                         "random initial weights (the time per iteration does not depend on them)")
     a = ap.parse_args()
     configs = a.configs.split(",")
     assert all(c in ENV for c in configs), f"configurations: {sorted(ENV)}"
@@ -50,6 +58,8 @@ def main():
     task = a.task
     env_cfg, train_cfg = task_registry.get_cfgs(task)
     env_cfg.env.num_envs = a.num_envs
+    if a.no_fused_update:
+        train_cfg.algorithm.use_fused_update = False
     cli = get_args(["--sim_device", "cuda:0", "--rl_device", "cuda:0", "--headless", "--task", task])
     out = {c: [] for c in configs}
     with tempfile.TemporaryDirectory() as tmp, open(os.devnull, "w") as null, contextlib.redirect_stdout(null):
@@ -59,9 +69,15 @@ def main():
             runners[logged], _ = task_registry.make_alg_runner(env, name=task, args=cli, train_cfg=train_cfg,
                                                                log_root=tmp if logged else None)
 
+        for r in runners.values():   # Distillation: a teacher (its values do not matter to the clock)
+            if hasattr(r.alg.actor_critic, "loaded_teacher"):
+                if a.teacher:
+                    r.load(a.teacher)
+                r.alg.actor_critic.loaded_teacher = True
+
         # symmetry augmentation (algorithm.symmetry): HIP events around each update's augment launch
         fused = [r.alg._fused for r in runners.values()
-                 if getattr(r.alg, "_fused", None) is not None and r.alg.storage.symmetry is not None]
+                 if getattr(r.alg, "_fused", None) is not None and getattr(r.alg.storage, "symmetry", None) is not None]
         for f in fused:
             f.time_augment = True
 
@@ -85,7 +101,7 @@ def main():
                                                          for k in ("collection_time", "learn_time")}
                   for logged, r in runners.items()}
         augment = [e0.elapsed_time(e1) * 1e3 for f in fused for e0, e1 in f.augment_events]
-    res = {"task": task, "num_envs": a.num_envs, "iters_per_window": a.iters, "warmup_iters": a.warmup,
+    res = {"task": task, "num_envs": a.num_envs, "fused_update": not a.no_fused_update, "iters_per_window": a.iters, "warmup_iters": a.warmup,
            "device": torch.cuda.get_device_name(0),
            "ms_per_iteration": {c: {"median": round(statistics.median(w), 4), "windows": w} for c, w in out.items()},
            "last_iteration_phases_ms": phases}
