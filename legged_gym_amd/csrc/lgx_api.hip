@@ -38,6 +38,7 @@ struct lgx_sim {
   bool dense;             // physics on lgx_physics_dense_kernel (leg_dof 6 / LGX_PHYS_DENSE=1)
   int pp;                 // lanes per leg of the arrowhead physics kernel (lgx_physics_pp at create)
   int act_mode;           // where the Go1 actuator net runs (LGX_ACT_OVERLAP at create)
+  int tm_mode;            // stage-2 form of the physics kernel's trimesh queue (LGX_TM_STAGE2 at create)
   int32_t num_points;     // contact candidates of the model (the dense kernel's LDS sizing)
   lgx_env_params params;  // host copy
   lgx_buffers bufs;
@@ -226,6 +227,16 @@ int lgx_sim_create(const lgx_model* model, const lgx_env_params* params, const l
   if (s->act_mode < 0 || s->act_mode > 2 || (am && *am && (am[0] < '0' || am[0] > '2' || am[1]))) {
     delete s;
     return fail(LGX_EINVAL, "lgx_sim_create: LGX_ACT_OVERLAP must be 0, 1 or 2");
+  }
+  // the stage-2 form of the corrected-trimesh queue (LGX_TM_STAGE2, read here once): unset = the
+  // kernel's automatic rule, or one form for every queue length (the forms give the same bits; A/B
+  // runs and the tests that hold them against each other)
+  const char* tm = getenv("LGX_TM_STAGE2");
+  s->tm_mode = !tm || !*tm ? LGX_TM_AUTO : !strcmp(tm, "rows") ? LGX_TM_ROWS : !strcmp(tm, "lane") ? LGX_TM_LANE
+               : !strcmp(tm, "packed") ? LGX_TM_PACKED : -1;
+  if (s->tm_mode < 0) {
+    delete s;
+    return fail(LGX_EINVAL, "lgx_sim_create: LGX_TM_STAGE2 must be rows, lane or packed");
   }
   s->num_points = model->num_points;
   s->params = *params;
@@ -541,11 +552,11 @@ int lgx_sync_aux(lgx_sim* s, void* stream) {
 static int physics(lgx_sim* s, int32_t nsub, int32_t from_actions, const float* actions, hipStream_t st, int32_t frozen) {
   if (s->arand.prev)   // actuator tables bound (never on the dense kernel: lgx_bind_actuator_rand)
     return lgx_launch_physics_rand(s->d_model, s->d_params, s->bufs, s->params.num_envs, nsub, from_actions, actions,
-                                   st, frozen, s->pp, s->arand);
+                                   st, frozen, s->pp, s->tm_mode, s->arand);
   return s->dense ? lgx_launch_physics_dense(s->d_model, s->d_params, s->bufs, s->params.num_envs, nsub, from_actions,
                                              actions, st, frozen, s->num_points)
                   : lgx_launch_physics(s->d_model, s->d_params, s->bufs, s->params.num_envs, nsub, from_actions, actions,
-                                       st, frozen, s->pp);
+                                       st, frozen, s->pp, s->tm_mode);
 }
 
 int lgx_simulate(lgx_sim* s, int32_t n, void* stream) {

@@ -23,9 +23,13 @@ int lgx_physics_pp(int32_t n_envs);   // lanes per leg of the physics launch at 
 // frozen != 0: only the drive inputs of `nsub` substeps (clip, targets, actuator-net history and
 // model_ins rows) with the state held fixed (lgx_drive_inputs)
 // pp: lanes per leg (lgx_physics_pp at lgx_sim_create)
+// tm_mode: the stage-2 form of the corrected-trimesh queue (LGX_TM_STAGE2 at lgx_sim_create): the
+// automatic rule, or one form for every queue length - 16 lanes per sphere, one lane per sphere, one
+// lane per (sphere, cell, triangle).  Every form gives the same bits.
+enum { LGX_TM_AUTO = 0, LGX_TM_ROWS = 1, LGX_TM_LANE = 2, LGX_TM_PACKED = 3 };
 int lgx_launch_physics(const lgx_dev_model* dm, const lgx_env_params* dp, const lgx_buffers& b, int32_t n_envs,
                        int32_t nsub, int32_t from_actions, const float* act_src, hipStream_t stream, int32_t frozen,
-                       int pp);
+                       int pp, int32_t tm_mode);
 // the per-env actuator tables of a sim (lgx_bind_actuator_rand, checked there), passed by value to
 // the physics launches of a sim that bound them; prev == nullptr: nothing bound.  kp_scale / kd_scale
 // [N,12] and lag [N] are the caller's (each may be nullptr: 1, 1, 0), prev [N,12] is the sim's: the
@@ -40,7 +44,7 @@ struct lgx_act_rand_args {
 // lgx_physics_kernel<PP, lgx_act_rand_args> instantiations
 int lgx_launch_physics_rand(const lgx_dev_model* dm, const lgx_env_params* dp, const lgx_buffers& b, int32_t n_envs,
                             int32_t nsub, int32_t from_actions, const float* act_src, hipStream_t stream,
-                            int32_t frozen, int pp, const lgx_act_rand_args& ar);
+                            int32_t frozen, int pp, int32_t tm_mode, const lgx_act_rand_args& ar);
 // the dense joint-space kernel (lgx_physics.hip): leg_dof == 6 robots, or any with LGX_PHYS_DENSE=1
 int lgx_launch_physics_dense(const lgx_dev_model* dm, const lgx_env_params* dp, const lgx_buffers& b, int32_t n_envs,
                              int32_t nsub, int32_t from_actions, const float* act_src, hipStream_t stream,

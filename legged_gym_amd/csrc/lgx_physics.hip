@@ -476,6 +476,48 @@ LGX_DEV void tm_init(TmQuery& q, f3 p) {
   q.top = -3.0e38f; q.tn = mk3(0.f, 0.f, 1.f);
 }
 
+// tm_cell_verts: the moved vertices of cell (ca, cb) of the 3 x 3 around (i, j) - tm_cell_tris' decode
+// for a cell tm_keep kept (on the map, not culled), so that its two triangles can go to two lanes
+LGX_DEV void tm_cell_verts(const lgx_env_params* __restrict__ P, const lgx_buffers& B, int i, int j, int ca, int cb,
+                           const int32_t* hpatch, int pi0, int pj0, f3* v) {
+  // rounded products, never contracted into the triangle's differences: tm_cell_tris' are not either
+  // (its cull branch stands between the products and tm_tri), and the bits must be its
+#pragma clang fp contract(off)
+  const float hs = P->horizontal_scale, vs = P->vertical_scale;
+  const int cols = B.hf_cols;
+  const int ci = i - 1 + ca, cj = j - 1 + cb;
+  int h[4], code[4];   // samples (ci + (k & 1), cj + (k >> 1))
+  if (hpatch && (unsigned)(ci - pi0) < LGX_HF_PATCH - 1 && (unsigned)(cj - pj0) < LGX_HF_PATCH - 1) {
+    const int32_t* w = hpatch + (ci - pi0) * LGX_HF_PATCH + (cj - pj0);
+    const int w0 = w[0], w1 = w[LGX_HF_PATCH], w2 = w[1], w3 = w[LGX_HF_PATCH + 1];
+    h[0] = w0 >> 8; h[1] = w1 >> 8; h[2] = w2 >> 8; h[3] = w3 >> 8;
+    code[0] = w0 & 15; code[1] = w1 & 15; code[2] = w2 & 15; code[3] = w3 & 15;
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int64_t o = (int64_t)(ci + (k & 1)) * cols + cj + (k >> 1);
+      h[k] = B.height_samples[o];
+      code[k] = B.hf_trimesh[o];
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) code[k] &= 15;
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int da = ca + (k & 1), db = cb + (k >> 1);
+    const int dx = ((code[k] * 11) >> 5) - 1, dy = code[k] - 3 * (dx + 1) - 1;
+    v[k] = mk3((float)(da - 1 + dx) * hs, (float)(db - 1 + dy) * hs, (float)h[k] * vs);
+  }
+}
+
+// one triangle's query state into the running one, in the order the sequential scan meets them: the
+// comparisons of tm_tri (strict: the first triangle keeps a tie).  A fresh query that its triangle
+// did not improve holds tm_init's values, which never pass either comparison.
+LGX_DEV void tm_merge(TmQuery& q, const TmQuery& o) {
+  if (o.d2 < q.d2) { q.d2 = o.d2; q.cp = o.cp; q.cn = o.cn; }
+  if (o.top > q.top) { q.top = o.top; q.tn = o.tn; }
+}
+
 // tm_finish: inside = p below the surface under it; depth = r -/+ distance, normal = from the surface
 // point toward p (outside) or from p toward it (inside); where p sits on the surface, the face normal
 LGX_DEV float tm_finish(const TmQuery& q, f3 p, float r, f3* n) {
@@ -657,6 +699,31 @@ LGX_DEV void wave_lds_sync() {
 #define LGX_PHYS_WAVES_PER_SIMD 1
 #endif
 #define HIST_STRIDE 31
+// The automatic choice among the forms of the corrected-trimesh queue (lgx_physics_kernel, tm_mode ==
+// LGX_TM_AUTO), by the wave's queue length qn and its length after stage 1, qn2.  A launch lasts as long
+// as its slowest wave, and the slowest waves are the ones that need a second 16-lane round (DESIGN 4.1,
+// profiles/trimesh_queue.json: a rows round 6.0 - 6.4 k cycles, two 10.3 - 12.0 k; one packed round of
+// 5 - 6 spheres 7.1 - 8.4 k; a one-lane round of 9 - 10 spheres 16.3 - 16.7 k; the cell culls in stage 1
+// 3.5 k against 1.4 k for the block-height test alone).  So: qn <= LGX_TM_CULL1_QN spheres fit one rows
+// round whatever stage 1 dismisses - the block-height test alone, then rows; longer queues get the cell
+// culls, and then qn2 <= LGX_TM_ROWS_QN2 is one rows round, qn2 <= LGX_TM_PACKED_QN2 packed (two packed
+// rounds cost one one-lane round, and 16 spheres of the typical <= 4 kept cells are 128 triples: two
+// rounds; measured up to qn2 = 10, reasoned beyond), anything longer one lane per sphere.  A tuning
+// build overrides them with -D.
+#ifndef LGX_TM_CULL1_QN
+#define LGX_TM_CULL1_QN 4
+#endif
+#ifndef LGX_TM_ROWS_QN2
+#define LGX_TM_ROWS_QN2 4
+#endif
+#ifndef LGX_TM_PACKED_QN2
+#define LGX_TM_PACKED_QN2 16
+#endif
+#ifdef LGX_PHASE_CLOCK_BUF
+// tuning builds: every wave's queue of the last launch, per (workgroup, wave, substep & 3):
+// qn << 16 | qn2, stage-1 cycles, stage-2 cycles, stage-2 form (1 rows, 2 lane, 3 packed; 0: empty queue)
+static __device__ unsigned lgx_tmq_buf[LGX_CLK_MAXB][8][4][4];
+#endif
 
 // sum over the PP lanes that share a leg (lane bits 2..): contact terms were split across them
 template <int PP>
@@ -696,7 +763,8 @@ LGX_DEV lgx_act_rand_args act_rand_of(const lgx_act_rand_args& a) { return a; }
 template <int PP, typename... AR>
 __global__ void __launch_bounds__(64 * PP, LGX_PHYS_WAVES_PER_SIMD)
 lgx_physics_kernel(const lgx_dev_model* __restrict__ DMg, const lgx_env_params* __restrict__ P, lgx_buffers B,
-                   int32_t nsub, int32_t from_actions, const float* __restrict__ act_src, int32_t frozen, AR... ar) {
+                   int32_t nsub, int32_t from_actions, const float* __restrict__ act_src, int32_t frozen,
+                   int32_t tm_mode, AR... ar) {
   static_assert(sizeof...(AR) <= 1, "at most the actuator tables");
   constexpr bool RAND = sizeof...(AR) == 1;
   constexpr int PHYS_BLOCK = 64 * PP;               // 16 envs per workgroup
@@ -722,6 +790,12 @@ lgx_physics_kernel(const lgx_dev_model* __restrict__ DMg, const lgx_env_params* 
   __shared__ int32_t hf_org[ENVS][2];
   // per-wave queue of the candidates that need the corrected-trimesh query: (cells << 16 | slot << 6 | lane)
   __shared__ uint32_t tm_q[PP][64 * SLOTS];
+  // the packed stage 2 of that queue, per wave: a round's 64 (sphere, cell, triangle) triples
+  // (sphere's lane << 5 | cell << 1 | triangle) and the query state each triple's lane leaves
+  // (d2, cp, cn, top, tn: 11 words, word-major - single registers on both sides, no 4-register tuples
+  // at the kernel's register ceiling)
+  __shared__ uint32_t tm_tl[PP][64];
+  __shared__ float tm_rec[PP][11][64];
   {
     static_assert(sizeof(lgx_dev_model) % 16 == 0, "the model is staged in 16-byte units");
     const int4* src = reinterpret_cast<const int4*>(DMg);
@@ -1149,15 +1223,22 @@ lgx_physics_kernel(const lgx_dev_model* __restrict__ DMg, const lgx_env_params* 
         qn += __popcll(m);
       }
       LGX_CLK(8);
+#ifdef LGX_PHASE_CLOCK_BUF
+      const uint64_t lgx_tmq_t0 = clock64();
+      uint64_t lgx_tmq_t1 = lgx_tmq_t0;
+      int lgx_tmq_form = 0, lgx_tmq_qn2 = 0;
+#endif
       if (qn > 0) {
         wave_lds_sync();
         // stage 1: which cells of the 3 x 3 each sphere has to visit, survivors compacted in place with
         // their cell set (a round reads all its entries before it writes any, and writes only
-        // positions below the ones it read).  Short queues (a Go1's feet): the block-height test
-        // alone (the spheres well above the ground leave), every cell kept - stage 2 culls them per
-        // lane; long queues (a capsule-covered robot like ANYmal on stairs): the cell culls too, so
-        // fewer spheres reach stage 2 and each visits only its kept cells
-        const bool cull1 = qn > 16;
+        // positions below the ones it read).  Up to LGX_TM_CULL1_QN spheres (one 16-lane round at
+        // most): the block-height test alone (the spheres well above the ground leave), every cell
+        // kept - stage 2 culls them per lane; longer queues: the cell culls too, so fewer spheres
+        // reach stage 2, each visits only its kept cells, and stage 2 is chosen by what is left.
+        // LGX_TM_STAGE2 (tm_mode) forces one stage-2 form for every queue length; the packed form
+        // needs the cell sets
+        const bool cull1 = tm_mode == LGX_TM_PACKED || qn > LGX_TM_CULL1_QN;
         int qn2 = 0;
         for (int q0 = 0; q0 < qn; q0 += 64) {
           const int q = q0 + ln;
@@ -1189,12 +1270,132 @@ lgx_physics_kernel(const lgx_dev_model* __restrict__ DMg, const lgx_env_params* 
 #ifdef LGX_PHASE_CLOCK
         lgx_clk_acc[11] += (uint64_t)qn * 1000 + qn2;   // queue lengths (tuning builds)
 #endif
-        // stage 2: the kept cells of each near sphere.  Few spheres (the common case: a robot's feet on
-        // a riser): 16 lanes per sphere, lane g < 9 of the row visits cell g if kept, the row combines
-        // in the sequential scan's order.  Many (a capsule-covered robot like ANYmal on stairs): one
-        // lane per sphere visiting its kept cells in order (a round costs its lane with the most
-        // cells, typically 1 - 3 of the 9)
-        if (qn2 <= 8) {
+#ifdef LGX_PHASE_CLOCK_BUF
+        lgx_tmq_t1 = clock64();
+        lgx_tmq_qn2 = qn2;
+#endif
+        // stage 2: the kept cells of each near sphere, in one of three forms that give the same bits
+        // (the rule and its thresholds: above, at LGX_TM_CULL1_QN).  Rows: 16 lanes per sphere, lane
+        // g < 9 of the row visits cell g if kept, the row combines in the sequential scan's order; 4
+        // spheres a round.  Lane: one lane per sphere visiting its kept cells in order (a round costs
+        // its lane with the most cells, typically 1 - 3 of the 9).  Packed: one lane per (sphere,
+        // kept cell, triangle), up to 64 triples a round, each lane a fresh query of one triangle
+        // left in the wave's LDS; the sphere's lane merges its records in list order - sphere,
+        // ascending cell, the reference triangle order, which is the sequential scan's - with
+        // tm_tri's own comparisons, so the result is the one-lane query's
+        const bool rows = tm_mode == LGX_TM_ROWS || (tm_mode == LGX_TM_AUTO && qn2 <= LGX_TM_ROWS_QN2);
+        const bool packed = tm_mode == LGX_TM_PACKED ||
+                            (tm_mode == LGX_TM_AUTO && cull1 && !rows && qn2 <= LGX_TM_PACKED_QN2);
+#ifdef LGX_PHASE_CLOCK_BUF
+        lgx_tmq_form = packed ? 3 : rows ? 1 : 2;
+#endif
+        if (packed) {
+          for (int b0 = 0; b0 < qn2; b0 += 64) {
+            // one lane per sphere of the batch; the lanes past the queue repeat its last entry and own
+            // no triple (clamped always-valid reads, the condition on the writes only)
+            const uint32_t ent = tm_q[wv][min(b0 + ln, qn2 - 1)];
+            const unsigned keep = b0 + ln < qn2 ? (ent >> 16) & 0x1ffu : 0u;
+            // own triples [start, end) of the batch's list: a prefix sum of 2 per kept cell, from the
+            // ballots of the cell count's four bits (no cross-lane data movement)
+            const int nc = __popc(keep);
+            int start = 0, total = 0;
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+              const uint64_t m = __ballot((nc >> b) & 1);
+              start += __popcll(m & below) << (b + 1);
+              total += __popcll(m) << (b + 1);
+            }
+            const int end = start + 2 * nc;
+            for (int r0 = 0; r0 < total;) {
+              // a round is the next 64 triples, cut back to whole spheres (at most 18 each): it ends
+              // where the sphere that would straddle its end starts, so no query outlives a round
+              const uint64_t cut = __ballot(start < r0 + 64 && end > r0 + 64);
+              const int rend = cut ? __builtin_amdgcn_readlane(start, (int)__builtin_ctzll(cut)) : min(total, r0 + 64);
+              const bool mine = start >= r0 && end <= rend && keep != 0u;
+              // list the round's triples (a wave-uniform trip count: the cells of its fullest sphere)
+              {
+                unsigned rem = mine ? keep : 0u;
+                int nxt = start - r0;
+                for (;;) {
+                  const bool on = rem != 0u;
+                  if (__ballot(on) == 0) break;
+                  if (on) {
+                    const uint32_t w = (uint32_t)(ln << 5 | __builtin_ctz(rem) << 1);
+                    tm_tl[wv][nxt] = w;
+                    tm_tl[wv][nxt + 1] = w | 1u;
+                    rem &= rem - 1;
+                    nxt += 2;
+                  }
+                }
+              }
+              wave_lds_sync();
+              {  // one triple per lane; the lanes past the round's list repeat its last triple
+                const uint32_t tr = tm_tl[wv][min(ln, rend - r0 - 1)];
+                const uint32_t ent3 = tm_q[wv][b0 + (int)(tr >> 5)];
+                const int sl3 = (ent3 >> 6) & 1023, t3 = (wv << 6) | (ent3 & 63), e3 = t3 / LPE;
+                const float4 g3 = geo_p[sl3][t3];
+                const f3 pw3 = mk3(g3.x, g3.y, g3.z) + mk3(env_com[e3][36], env_com[e3][37], env_com[e3][38]);
+                const int32_t* hp = use_patch ? hf_patch[e3] : nullptr;
+                const int o0 = use_patch ? hf_org[e3][0] : 0, o1 = use_patch ? hf_org[e3][1] : 0;
+                int i3, j3;
+                tm_cell(P, B, pw3, &i3, &j3);
+                const f3 p3 = tm_local(P, pw3, i3, j3);
+                const int c = (tr >> 1) & 15, ca = (c * 11) >> 5;
+                f3 v[4];
+                tm_cell_verts(P, B, i3, j3, ca, c - 3 * ca, hp, o0, o1, v);
+                const bool second = (tr & 1u) != 0u;   // (v0, v3, v2) first, then (v0, v1, v3)
+                TmQuery tq;
+                tm_init(tq, p3);
+                tm_tri(tq, p3, v[0], second ? v[1] : v[3], second ? v[3] : v[2]);
+                const float w[11] = {tq.d2, tq.cp.x, tq.cp.y, tq.cp.z, tq.cn.x, tq.cn.y, tq.cn.z, tq.top, tq.tn.x, tq.tn.y, tq.tn.z};
+#pragma unroll
+                for (int k = 0; k < 11; ++k) tm_rec[wv][k][ln] = w[k];
+              }
+              wave_lds_sync();
+              // each sphere of the round: its records merged in list order (a wave-uniform trip count,
+              // clamped reads), then the query's end as in the other forms
+              const int sl2 = (ent >> 6) & 1023, t = (wv << 6) | (ent & 63), e2 = t / LPE;
+              const float4 gp = geo_p[sl2][t];
+              const f3 Pp = mk3(gp.x, gp.y, gp.z);
+              const f3 pw = Pp + mk3(env_com[e2][36], env_com[e2][37], env_com[e2][38]);
+              int i, j;
+              tm_cell(P, B, pw, &i, &j);
+              const f3 pl3 = tm_local(P, pw, i, j);
+              TmQuery run;
+              tm_init(run, pl3);
+              int p = mine ? start - r0 : 0;
+              const int pe = mine ? end - r0 : 0;
+              for (;;) {
+                const bool on = p < pe;
+                if (__ballot(on) == 0) break;
+                const int pc = on ? p : 0;
+                float w[11];
+#pragma unroll
+                for (int k = 0; k < 11; ++k) w[k] = tm_rec[wv][k][pc];
+                if (on) {
+                  TmQuery o;
+                  o.d2 = w[0]; o.cp = mk3(w[1], w[2], w[3]);
+                  o.cn = mk3(w[4], w[5], w[6]); o.top = w[7];
+                  o.tn = mk3(w[8], w[9], w[10]);
+                  tm_merge(run, o);
+                }
+                ++p;
+              }
+              if (mine) {
+                f3 n;
+                const float depth = tm_finish(run, pl3, gp.w, &n);
+                slot_state[sl2][t] = make_float4(depth > 0.f ? 1.f : 0.f, 0.f, 0.f, 0.f);
+                if (depth > 0.f) {
+                  const f3 Pc = Pp - gp.w * n;
+                  geo_p[sl2][t] = make_float4(Pc.x, Pc.y, Pc.z, depth);
+                  geo_n[sl2][t] = make_float4(n.x, n.y, n.z, geo_n[sl2][t].w);
+                }
+              }
+              wave_lds_sync();
+              r0 = rend;
+            }
+          }
+        } else if (rows) {
           const int grp = ln >> 4, g = ln & 15;
           for (int q0 = 0; q0 < qn2; q0 += 4) {
             const int q = min(q0 + grp, qn2 - 1);
@@ -1254,6 +1455,15 @@ lgx_physics_kernel(const lgx_dev_model* __restrict__ DMg, const lgx_env_params* 
         }
       }
       wave_lds_sync();
+#ifdef LGX_PHASE_CLOCK_BUF
+      if (ln == 0 && blockIdx.x < LGX_CLK_MAXB) {
+        unsigned* r = lgx_tmq_buf[blockIdx.x][wv & 7][s & 3];
+        r[0] = (unsigned)qn << 16 | (unsigned)lgx_tmq_qn2;
+        r[1] = (unsigned)(lgx_tmq_t1 - lgx_tmq_t0);
+        r[2] = (unsigned)(clock64() - lgx_tmq_t1);
+        r[3] = (unsigned)lgx_tmq_form;
+      }
+#endif
     }
     // this lane's active list for the substep (bit = own slot): every own slot's status is 0 or 1 by
     // now (all slots read before the first is used; the slots past the leg's candidates hold nothing
@@ -1491,22 +1701,22 @@ lgx_physics_kernel(const lgx_dev_model* __restrict__ DMg, const lgx_env_params* 
 
 int lgx_launch_physics_rand(const lgx_dev_model* dm, const lgx_env_params* dp, const lgx_buffers& b, int32_t n_envs,
                             int32_t nsub, int32_t from_actions, const float* act_src, hipStream_t stream,
-                            int32_t frozen, int ppx, const lgx_act_rand_args& ar) {
+                            int32_t frozen, int ppx, int32_t tm_mode, const lgx_act_rand_args& ar) {
   if (!ar.prev) return -1;
   if (!act_src) act_src = b.actions;
   const int blocks = (n_envs + 15) / 16;       // 16 envs per workgroup of 64*PP lanes
   if (ppx == 8)
     LGX_LAUNCH((lgx_physics_kernel<8, lgx_act_rand_args>), dim3(blocks), dim3(512), 0, stream, dm, dp, b, nsub,
-               from_actions, act_src, frozen, ar);
+               from_actions, act_src, frozen, tm_mode, ar);
   else if (ppx == 4)
     LGX_LAUNCH((lgx_physics_kernel<4, lgx_act_rand_args>), dim3(blocks), dim3(256), 0, stream, dm, dp, b, nsub,
-               from_actions, act_src, frozen, ar);
+               from_actions, act_src, frozen, tm_mode, ar);
   else if (ppx == 2)
     LGX_LAUNCH((lgx_physics_kernel<2, lgx_act_rand_args>), dim3(blocks), dim3(128), 0, stream, dm, dp, b, nsub,
-               from_actions, act_src, frozen, ar);
+               from_actions, act_src, frozen, tm_mode, ar);
   else
     LGX_LAUNCH((lgx_physics_kernel<1, lgx_act_rand_args>), dim3(blocks), dim3(64), 0, stream, dm, dp, b, nsub,
-               from_actions, act_src, frozen, ar);
+               from_actions, act_src, frozen, tm_mode, ar);
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
@@ -1546,17 +1756,17 @@ int lgx_physics_pp(int32_t n_envs) {
 
 int lgx_launch_physics(const lgx_dev_model* dm, const lgx_env_params* dp, const lgx_buffers& b, int32_t n_envs,
                        int32_t nsub, int32_t from_actions, const float* act_src, hipStream_t stream, int32_t frozen,
-                       int ppx) {
+                       int ppx, int32_t tm_mode) {
   if (!act_src) act_src = b.actions;
   const int blocks = (n_envs + 15) / 16;       // 16 envs per workgroup of 64*PP lanes
   if (ppx == 8)
-    LGX_LAUNCH(lgx_physics_kernel<8>, dim3(blocks), dim3(512), 0, stream, dm, dp, b, nsub, from_actions, act_src, frozen);
+    LGX_LAUNCH(lgx_physics_kernel<8>, dim3(blocks), dim3(512), 0, stream, dm, dp, b, nsub, from_actions, act_src, frozen, tm_mode);
   else if (ppx == 4)
-    LGX_LAUNCH(lgx_physics_kernel<4>, dim3(blocks), dim3(256), 0, stream, dm, dp, b, nsub, from_actions, act_src, frozen);
+    LGX_LAUNCH(lgx_physics_kernel<4>, dim3(blocks), dim3(256), 0, stream, dm, dp, b, nsub, from_actions, act_src, frozen, tm_mode);
   else if (ppx == 2)
-    LGX_LAUNCH(lgx_physics_kernel<2>, dim3(blocks), dim3(128), 0, stream, dm, dp, b, nsub, from_actions, act_src, frozen);
+    LGX_LAUNCH(lgx_physics_kernel<2>, dim3(blocks), dim3(128), 0, stream, dm, dp, b, nsub, from_actions, act_src, frozen, tm_mode);
   else
-    LGX_LAUNCH(lgx_physics_kernel<1>, dim3(blocks), dim3(64), 0, stream, dm, dp, b, nsub, from_actions, act_src, frozen);
+    LGX_LAUNCH(lgx_physics_kernel<1>, dim3(blocks), dim3(64), 0, stream, dm, dp, b, nsub, from_actions, act_src, frozen, tm_mode);
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
@@ -2143,7 +2353,13 @@ int lgx_launch_physics_dense(const lgx_dev_model* dm, const lgx_env_params* dp, 
 }
 
 #ifdef LGX_PHASE_CLOCK_BUF
-// instrumented builds only (tools/phase_clock.sh): the per-workgroup clock table of the last physics launch
+// instrumented builds only (tools/phase_clock.sh): every wave's trimesh-queue record of the last physics
+// launch, [nblocks][8 waves][4 substeps][4 words] (lgx_tmq_buf)
+extern "C" int lgx_debug_tmq(unsigned* out, int32_t nblocks) {
+  return hipMemcpyFromSymbol(out, HIP_SYMBOL(lgx_tmq_buf), (size_t)min(nblocks, LGX_CLK_MAXB) * 8 * 4 * 4 * 4, 0,
+                             hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
+}
+// the per-workgroup clock table of the last physics launch
 extern "C" int lgx_debug_clock(unsigned long long* out, int32_t nblocks) {
   return hipMemcpyFromSymbol(out, HIP_SYMBOL(lgx_clk_buf), (size_t)min(nblocks, LGX_CLK_MAXB) * 14 * 8, 0,
                              hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
